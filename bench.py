@@ -9,6 +9,8 @@ MLUPS = (M-1)(N-1) * steps / time / 1e6, whole-job aggregate.  The grid is fixed
 x^2 + 4y^2 < 1, zero initial guess (there is no dataset).
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full       # + iters-to-tol and the solution error
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs out/   # out/w.npy, out/state.npy
     python bench.py --gpus 8                  # spawns 8 ranks itself (one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         --master-port 29500 bench.py --gpus 8 --steps 200 --warmup 20
@@ -39,10 +41,21 @@ replayed graphs (`timed_path`); if every rung fails it is still printed, with va
 valid false.  A run whose rank count differs from --gpus fails; it never measures fewer GPUs than it
 reports.
 
-After the timed region a full solve to ||w^{k+1}-w^k|| < 1e-6 reports iters-to-tol and the error
-of the solution against the analytic u = (1 - x^2 - 4y^2)/10 (l2_error, max_error; disable with
---no-tol-solve).  That stop rule is the reference's absolute one: at fine grids it ends well before
-discretisation accuracy (32768^2: L2 error 5.7e-3), exactly as the reference's solver would.
+A plain run does what the headline figure needs and no more: setup, warmup, the timed steps, the
+JSON line.  With --full, a full solve to ||w^{k+1}-w^k|| < 1e-6 follows the timed region and reports
+iters-to-tol and the error of the solution against the analytic u = (1 - x^2 - 4y^2)/10 (l2_error,
+max_error; disable with --no-tol-solve, or ask for it alone with --tol-solve).  That stop rule is
+the reference's absolute one: at fine grids it ends well before discretisation accuracy (32768^2:
+L2 error 5.7e-3), exactly as the reference's solver would.
+
+--dump-outputs DIR writes what the timed path holds after its last timed step, before anything
+else runs: the iterate w of this rank's block (interior points, row-major) as DIR/w.npy (float64;
+DIR/w_rank<r>.npy per rank on several GPUs) and the solver state a caller reads back (iteration
+counter, ||w^{k+1}-w^k||, stop and NaN flags) as DIR/state.npy.  The ranks share one budget of
+DUMP_MAX_POINTS points (32 MB of float64 in all): a block of more than DUMP_MAX_POINTS // ranks points
+is written as a fixed sample of at most that many, the points at the sorted flat indices that
+numpy.random.default_rng(DUMP_SEED) draws, the same for every run of the same grid and rank count.  The problem is
+analytic (no random data), so the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -74,7 +87,7 @@ RUNGS = {
 # / IPC initialisation watchdog + 15 s).  No phase of a healthy 16384^2 run comes close: setup
 # (process group, solver, placement probe) takes ~5-20 s, the rest is sub-second per poll.
 DEADLINES = {"setup": 120, "comm-init": 105, "canary": 60, "first-batch": 60, "warmup": 60, "timed": 60,
-             "tol-solve": 60, "accuracy": 90, "profile": 300, "report": 60, "shutdown": 60}
+             "dump": 120, "tol-solve": 60, "accuracy": 90, "profile": 300, "report": 60, "shutdown": 60}
 COMM_INIT_TIMEOUT = 90.0  # DistGpuPCG's own watchdog around the blocking RCCL / IPC initialisation
 # Hard per-rung limits of the supervisor (a rung normally ends far earlier: success in ~30-60 s, a
 # hang at its phase deadline).  Worst case rung 1 + rung 2 = 360 s of a 540-s ladder budget.
@@ -122,7 +135,14 @@ def parse(argv=None):
     ap.add_argument("--overlap", default="on", choices=["on", "off"],
                     help="ghost exchange on a second HIP stream, overlapped with the sweep")
     ap.add_argument("--exact", action="store_true", help="reference arithmetic order in the fused kernels")
-    ap.add_argument("--tol-solve", dest="tol_solve", action="store_true", default=True)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: the solve "
+                         "to tolerance with iters-to-tol and the error against the analytic solution")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the iterate and the solver state after the last timed step as DIR/<name>.npy "
+                         "(see the module docstring)")
+    ap.add_argument("--tol-solve", dest="tol_solve", action="store_true", default=None,
+                    help="the solve to tolerance (default: only with --full)")
     ap.add_argument("--no-tol-solve", dest="tol_solve", action="store_false")
     ap.add_argument("--tol-time-cap", type=float, default=100.0, help="seconds allowed for the tol solve")
     ap.add_argument("--json-out", default=None)
@@ -158,7 +178,10 @@ def parse(argv=None):
     ap.add_argument("--placement-budget", type=float, default=0.5, help="placement probe: seconds of probing")
     ap.add_argument("--placement-keep-free", type=float, default=0.25,
                     help="placement probe: fraction of the free device memory left free")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.tol_solve is None:
+        args.tol_solve = args.full
+    return args
 
 
 # =============================================================================================
@@ -275,7 +298,7 @@ def _ladder(args) -> list[int]:
 
 # phases in the order a rank passes them (the least advanced rank of a failed rung is its cause: the
 # others wait for it in a collective and time out in a later phase)
-PHASE_ORDER = ("start", "setup", "comm-init", "canary", "first-batch", "warmup", "timed", "tol-solve",
+PHASE_ORDER = ("start", "setup", "comm-init", "canary", "first-batch", "warmup", "timed", "dump", "tol-solve",
                "accuracy", "profile", "report", "shutdown")
 
 
@@ -508,6 +531,46 @@ def supervise(args) -> int:
 # =============================================================================================
 # measuring rank
 # =============================================================================================
+DUMP_MAX_POINTS = 4 * 1024 * 1024  # 32 MB of float64 for ALL ranks together (each: DUMP_MAX_POINTS // world)
+DUMP_SEED = 20240607
+
+
+def dump_rank_points(world: int) -> int:
+    """Points one of `world` ranks may write: the dump of the whole job stays within DUMP_MAX_POINTS."""
+    return DUMP_MAX_POINTS // max(1, int(world))
+
+
+def dump_sample(w, max_points: int = DUMP_MAX_POINTS, seed: int = DUMP_SEED):
+    """The flat float64 array --dump-outputs writes for the block `w`: all of it, or the points at
+    the sorted distinct flat indices of max_points seeded draws (a function of w.size alone)."""
+    import numpy as np
+
+    flat = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    if flat.size <= max_points:
+        return flat
+    idx = np.unique(np.random.default_rng(seed).integers(0, flat.size, size=max_points))
+    return flat[idx]
+
+
+def dump_outputs(path: str, runner, state: dict, rank: int, world: int) -> None:
+    """DIR/w[_rank<r>].npy and DIR/state[_rank<r>].npy of the solver as the timed region left it."""
+    import numpy as np
+
+    if hasattr(runner, "local_w"):  # DistGpuPCG
+        w = runner.local_w()
+    elif hasattr(runner, "s"):  # SessionRunner: the single-process native Session
+        w = runner.s.local_w(0)
+    else:  # TorchRunner (CPU dry run): the padded block without its ghost frame
+        w = runner.pcg.w[1:-1, 1:-1].detach().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"w{tag}.npy"), dump_sample(w, max_points=dump_rank_points(world)))
+    diff = float(state["diff"])  # -1 when the solver has none yet: a NaN would never compare equal
+    np.save(os.path.join(path, f"state{tag}.npy"),
+            np.array([float(state["it"]), diff if np.isfinite(diff) else -1.0,
+                      float(bool(state["done"])), float(bool(state["nan"]))], dtype=np.float64))
+
+
 def measure(args) -> int:
     import importlib
 
@@ -673,7 +736,12 @@ def measure(args) -> int:
     pts = (args.M - 1) * (args.N - 1)
     mlups = pts * args.steps / dt / 1e6
 
-    # ---------------- iterations to tolerance + accuracy ----------------
+    # ---------------- the timed path's outputs (before anything else touches the solver) ----------------
+    if args.dump_outputs:
+        watch.phase("dump")
+        dump_outputs(args.dump_outputs, runner, st1, info.rank, world)
+
+    # ---------------- iterations to tolerance + accuracy (--full) ----------------
     tol = {}
     if args.tol_solve:
         watch.phase("tol-solve")

@@ -59,20 +59,20 @@ STUDIES: dict[str, list[tuple[str, int, str]]] = {
     # round-3 first contact: launch path, ladder, accuracy; the default bench; an 8-rank rehearsal
     "launch": [
         ("pytest_launch", 420, f"{PYTEST} tests/test_gpu_launch_path.py"),
-        ("bench_default", 300, bench("--gpus 1 --steps 20 --warmup 5")),
-        ("share8", 420, bench("--gpus 8 --share-gpu --M 4096 --N 4096 --steps 20 --warmup 5")),
+        ("bench_default", 300, bench("--gpus 1 --steps 20 --warmup 5 --full")),
+        ("share8", 420, bench("--gpus 8 --share-gpu --M 4096 --N 4096 --steps 20 --warmup 5 --full")),
     ],
     # the whole GPU suite as the driver runs it
     "ipc": [
         ("pytest_ipc", 600, f"{PYTEST} tests/test_gpu_dist.py -k 'ipc or share'"),
         ("pytest_launch", 420, f"{PYTEST} tests/test_gpu_launch_path.py -k 'bench'"),
-        ("share8", 420, bench("--gpus 8 --share-gpu --M 4096 --N 4096 --steps 20 --warmup 5")),
+        ("share8", 420, bench("--gpus 8 --share-gpu --M 4096 --N 4096 --steps 20 --warmup 5 --full")),
     ],
     "pytest_gpu": [
         ("pytest_gpu", 1100, f"{PYTEST} tests -m gpu"),
     ],
     "bench": [
-        ("bench_default", 300, bench("--gpus 1 --steps 20 --warmup 5")),
+        ("bench_default", 300, bench("--gpus 1 --steps 20 --warmup 5 --full")),
         ("bench_200", 300, bench("--gpus 1 --steps 200 --warmup 20 --no-tol-solve")),
     ],
     # binary A/B against a build of the previous commit copied to bench/ab/pmx_base (gitignored)
@@ -106,10 +106,10 @@ STUDIES: dict[str, list[tuple[str, int, str]]] = {
     ],
     # standalone bench records (BASELINE configs 2/5 and the headline)
     "records": [
-        ("bench_default", 300, bench("--gpus 1 --steps 20 --warmup 5")),
-        ("fp32_16384", 300, bench("--gpus 1 --dtype fp32 --steps 200 --warmup 20")),
-        ("fp32_32768", 500, bench("--gpus 1 --dtype fp32 --M 32768 --N 32768 --steps 100 --warmup 10")),
-        ("fp64_4096", 200, bench("--gpus 1 --M 4096 --N 4096 --steps 200 --warmup 20")),
+        ("bench_default", 300, bench("--gpus 1 --steps 20 --warmup 5 --full")),
+        ("fp32_16384", 300, bench("--gpus 1 --dtype fp32 --steps 200 --warmup 20 --full")),
+        ("fp32_32768", 500, bench("--gpus 1 --dtype fp32 --M 32768 --N 32768 --steps 100 --warmup 10 --full")),
+        ("fp64_4096", 200, bench("--gpus 1 --M 4096 --N 4096 --steps 200 --warmup 20 --full")),
     ],
     "profile_default": [
         ("rocprof_bench", 300, f"{ROCPROF} -d gpurun_out/profile_default/rp -o run -- "
@@ -197,7 +197,7 @@ def _validate(argv):
     py = PYTEST.replace(" -x ", " ") if keep else PYTEST
     return [("pytest_gpu", 1100, f"{py} tests -m gpu"),
             ("smoke", 200, "python -c 'import __graft_entry__ as g; g.smoke()'"),
-            ("bench_default", 300, bench(f"--gpus 1 --steps 20 --warmup 5 {extra}"))]
+            ("bench_default", 300, bench(f"--gpus 1 --steps 20 --warmup 5 --full {extra}"))]
 
 
 def _share(argv):
@@ -207,7 +207,8 @@ def _share(argv):
         lead += 1
     ranks = [int(x) for x in argv[:lead]] or [2, 4, 8]
     extra = " ".join(argv[lead:])
-    return [(f"share{n}", 420, bench(f"--gpus {n} --share-gpu --steps 20 --warmup 5 {extra}")) for n in ranks]
+    return [(f"share{n}", 420, bench(f"--gpus {n} --share-gpu --steps 20 --warmup 5 --full {extra}"))
+            for n in ranks]
 
 
 def _cli(argv):
@@ -239,7 +240,7 @@ def _ca_ab(argv):
 def _algos(argv):
     """bench.py per grid x algorithm x dtype: MxN:algo:dtype ... [-- bench.py args]"""
     cut = argv.index("--") if "--" in argv else len(argv)
-    extra = " ".join(argv[cut + 1:]) or "--steps 20 --warmup 5"
+    extra = " ".join(argv[cut + 1:]) or "--steps 20 --warmup 5 --full"
     steps = []
     for spec in argv[:cut]:
         g, algo, dt = spec.split(":")

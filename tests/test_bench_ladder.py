@@ -15,7 +15,8 @@ import pytest
 
 from conftest import ROOT, free_port
 
-BASE = ["--cpu-dry-run", "--M", "64", "--N", "96", "--steps", "4", "--warmup", "1", "--deadline-scale", "0.05"]
+BASE = ["--cpu-dry-run", "--full", "--M", "64", "--N", "96", "--steps", "4", "--warmup", "1", "--deadline-scale",
+        "0.05"]
 
 
 def _env(fault=None):

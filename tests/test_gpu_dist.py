@@ -71,8 +71,8 @@ def test_native_multiprocess_odd_blocks(pkg, tmp_path):
 def test_bench_share_gpu_rehearsal(tmp_path):
     """bench.py --gpus 2 spawns its own ranks; --share-gpu runs them on GPU 0 over the IPC transport
     (valid=false)."""
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--share-gpu", "--M", "512", "--N", "512",
-                        "--steps", "20", "--warmup", "4", "--tol-time-cap", "60", "--profile-phases", "8"],
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--share-gpu", "--full", "--M", "512", "--N",
+                        "512", "--steps", "20", "--warmup", "4", "--tol-time-cap", "60", "--profile-phases", "8"],
                        cwd=ROOT, capture_output=True, text=True, timeout=170)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith("{")]

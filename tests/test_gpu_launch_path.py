@@ -254,20 +254,52 @@ def _bench(args, timeout=300):
 
 
 def test_bench_times_the_graph_path(pkg):
-    j = _bench(["--gpus", "1", "--M", "1024", "--N", "1024", "--steps", "20", "--warmup", "5"])
+    j = _bench(["--gpus", "1", "--full", "--M", "1024", "--N", "1024", "--steps", "20", "--warmup", "5"])
     assert j["timed_path"] == "graph" and j["timed_graph_lengths"] == [20] and j["timed_eager_iters"] == 0
     assert j["valid"] and j["tol_status"] == "converged"
     assert 0 < j["l2_error"] < 1e-3 and j["max_error"] > 0
 
 
-def test_bench_share_gpu_rehearsal_supervised(pkg):
-    j = _bench(["--gpus", "2", "--share-gpu", "--M", "512", "--N", "512", "--steps", "10", "--warmup", "2"])
+def test_bench_plain_run_dumps_the_timed_iterate(pkg, tmp_path):
+    """A plain run (no --full) ends after the timed steps: no tol solve, no error norms.
+    --dump-outputs holds the iterate after warmup + steps iterations -- bit for bit the one a session
+    stepped that far returns (same kernels in the same order; graph lengths and the placement of the
+    fields do not enter the arithmetic, see the graph-vs-eager tests above)."""
+    M, N = 1024, 768
+    j = _bench(["--gpus", "1", "--M", str(M), "--N", str(N), "--steps", "20", "--warmup", "5", "--dump-outputs",
+                str(tmp_path)])
+    assert j["valid"] and j["timed_path"] == "graph" and j["steps"] == 20 and j["ms_per_step"] > 0
+    assert not {"tol_status", "iters_to_tol", "l2_error", "max_error"} & set(j)
+    assert sorted(os.listdir(tmp_path)) == ["state.npy", "w.npy"]
+    w, st = np.load(tmp_path / "w.npy"), np.load(tmp_path / "state.npy")
+    s = _session(pkg, M, N, graph_batch=32, split="auto")
+    assert s.tile["algo"] == j["config"]["tile"]["algo"]
+    s.init()
+    s.step(25)
+    s.synchronize()
+    ref = s.local_w(0).reshape(-1)
+    assert w.dtype == np.float64 and w.shape == ref.shape == ((M - 1) * (N - 1),)
+    assert np.abs(ref).max() > 0 and np.array_equal(w, ref)
+    state = s.state(0)
+    assert st[0] == state["it"] and st[1] == state["diff"] and st[2] == 0 and st[3] == 0
+
+
+def test_bench_share_gpu_rehearsal_supervised(pkg, tmp_path):
+    j = _bench(["--gpus", "2", "--share-gpu", "--full", "--M", "512", "--N", "512", "--steps", "10", "--warmup",
+                "2", "--dump-outputs", str(tmp_path)])
+    # every rank dumps its own block (whole at this size) and its state, taken before the tol solve
+    assert sorted(os.listdir(tmp_path)) == ["state_rank0.npy", "state_rank1.npy", "w_rank0.npy", "w_rank1.npy"]
+    blocks = [np.load(tmp_path / f"w_rank{r}.npy") for r in range(2)]
+    assert sum(b.size for b in blocks) == 511 * 511
+    assert all(b.dtype == np.float64 and np.abs(b).max() > 0 for b in blocks)
+    states = [np.load(tmp_path / f"state_rank{r}.npy") for r in range(2)]
+    assert np.array_equal(states[0], states[1]) and states[0][2] == 0 and 0 < states[0][0] < 20
     # RCCL refuses two ranks on one device: the rehearsal starts at the IPC transport (rung 3)
     assert j["n_gpus"] == 2 and j["config"]["rung"] == 3 and j["ladder"][0]["ok"]
     assert j["config"]["comm"] == "ipc" and j["valid"] is False
     assert j["timed_path"] == "graph" and j["config"]["split_sweep"] is True
     assert j["tol_status"] == "converged" and j["l2_error"] > 0
-    g = _bench(["--gpus", "2", "--share-gpu", "--comm", "torch", "--M", "512", "--N", "512", "--steps", "10",
-                "--warmup", "2"])
+    g = _bench(["--gpus", "2", "--share-gpu", "--full", "--comm", "torch", "--M", "512", "--N", "512", "--steps",
+                "10", "--warmup", "2"])
     assert g["config"]["rung"] == 4 and g["config"]["comm"] == "gloo-host-staged"
     assert g["iters_to_tol"] == j["iters_to_tol"]
