@@ -2,7 +2,7 @@
 session (its own field allocation), times `--iters` iterations after a warmup, in `--rounds`
 interleaved rounds; prints ms/iteration per configuration and the medians.
 
-  python bench/probe/ca_env_ab.py --n 16384 base: fuse:PMX_CA_FUSE=1,PMX_CA_WAVES_F=1
+  python bench/probe/ca_env_ab.py --n 16384 base: nosplit:PMX_CA_SPLIT_F=0 unfused:PMX_CA_FUSE=0
 """
 import argparse
 import importlib

@@ -229,6 +229,58 @@ __device__ __forceinline__ double dpp_shift0(double v) {
   return __longlong_as_double((long long)(unsigned)lo | ((long long)hi << 32));
 }
 
+// ---- pieces the marches share (ca_march: pass 1 / pass 2 / rewind; ca_march_fused: both waves) ----
+
+// A tile is "fast" when rows i0 - r .. i1 + r and its 128 loaded columns j0 - he .. j0 - he + 127 lie
+// strictly inside the grid and it owns the full width wo: no Dirichlet node or partial width in reach
+// (r: the march's radius, s or 2s).  k_ca_sweep's branch and make_ca_tiles' checks of both interior
+// rectangles; k_ca_fused spells the same condition out (see there).
+__host__ __device__ inline bool ca_tile_fast(const DevGeom& G, int i0, int i1, int j0, int j1, int r, int he, int wo) {
+  return j1 == j0 + wo - 1 && G.gi0 + i0 - r >= 1 && G.gi0 + i1 + r <= G.M - 1 && G.gj0 + j0 - he >= 1 &&
+         G.gj0 + j0 - he + 127 <= G.N - 1;
+}
+
+// Y = every level of both chains at the row in window slot sl (complete S steps after the row's load)
+template <int S, int sl>
+__device__ __forceinline__ void ca_gather(const double (&XP)[S + 1][4][2], const double (&XZ)[S][4][2],
+                                          double (&Y)[CaShape<S>::NB][2]) {
+#pragma unroll
+  for (int l = 0; l <= S; ++l) {
+    Y[l][0] = XP[l][sl][0];
+    Y[l][1] = XP[l][sl][1];
+  }
+#pragma unroll
+  for (int l = 0; l < S; ++l) {
+    Y[S + 1 + l][0] = XZ[l][sl][0];
+    Y[S + 1 + l][1] = XZ[l][sl][1];
+  }
+}
+
+// v0 + sum_i c_i Y_i at column u of a row: p = Y ca, z = Y cb, w += Y cc
+template <int NB>
+__device__ __forceinline__ double ca_dot(const double (&c)[NB], const double (&Y)[NB][2], int u, double v0) {
+#pragma unroll
+  for (int i = 0; i < NB; ++i) v0 = __builtin_fma(c[i], Y[i][u], v0);
+  return v0;
+}
+
+// ||p_{k+j}||^2 at column u of a row into acc[j], j = 0 .. S-1: p_{k+j} = Y a_j, and a_j lives on
+// P_0..P_j, Z_0..Z_{j-1} (a_0 = e_0)
+template <int S, int N>
+__device__ __forceinline__ void ca_norms(const double (&pa)[S][CaShape<S>::NB], const double (&Y)[CaShape<S>::NB][2],
+                                         int u, double (&acc)[N]) {
+  acc[0] = __builtin_fma(Y[0][u], Y[0][u], acc[0]);
+#pragma unroll
+  for (int j = 1; j < S; ++j) {
+    double v = 0.0;
+#pragma unroll
+    for (int i = 0; i <= j; ++i) v = __builtin_fma(pa[j][i], Y[i][u], v);
+#pragma unroll
+    for (int i = 0; i < j; ++i) v = __builtin_fma(pa[j][S + 1 + i], Y[S + 1 + i][u], v);
+    acc[j] = __builtin_fma(v, v, acc[j]);
+  }
+}
+
 template <typename T, int S, bool UPD>
 struct CaRow {
   T p[2], z[2], w[2];
@@ -246,23 +298,20 @@ __device__ __forceinline__ void ca_march(const DevGeom& G, const DevTables& Tb, 
                                          const double (&cb)[CaShape<S>::NB], const double (&cc)[CaShape<S>::NB],
                                          const double (&pa)[S][CaShape<S>::NB], double* dring = nullptr) {
   using Sh = CaShape<S>;
-  constexpr int NB = Sh::NB, A = Sh::AGES;
+  constexpr int NB = Sh::NB;
   const int64_t P = G.pitch;
   const int lane = threadIdx.x & 63;
   const int c0 = j0 - HE + 2 * lane;
   const int cmax = ca_cmax(G, F);
   bool colin[2], own[2];
-  int gj[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int c = c0 + u, g = G.gj0 + c;
     colin[u] = g >= 1 && g <= G.N - 1;
     own[u] = c >= j0 && c <= j1;
-    gj[u] = min(max(g, 0), G.N);
   }
   const bool own_all = own[0] && own[1];
   const bool own_any = own[0] || own[1];
-  auto grow = [&](int m) { return min(max(G.gi0 + m, 0), G.M); };
   auto interior_row = [&](int m) { return G.gi0 + m >= 1 && G.gi0 + m <= G.M - 1; };
 
   auto fetch = [&](int m, CaRow<T, S, UPD>& b) {
@@ -335,16 +384,7 @@ __device__ __forceinline__ void ca_march(const DevGeom& G, const DevTables& Tb, 
     if (g < i0 || g > i1) return;
     constexpr int sg = (q - S) & 3;
     double Y[NB][2];
-#pragma unroll
-    for (int l = 0; l <= S; ++l) {
-      Y[l][0] = XP[l][sg][0];
-      Y[l][1] = XP[l][sg][1];
-    }
-#pragma unroll
-    for (int l = 0; l < S; ++l) {
-      Y[S + 1 + l][0] = XZ[l][sg][0];
-      Y[S + 1 + l][1] = XZ[l][sg][1];
-    }
+    ca_gather<S, sg>(XP, XZ, Y);
     if constexpr (!UPD) {
       double d[2];
       ca_diag(ch[sg], g, K, G, F, c0, cmax, d);
@@ -359,32 +399,13 @@ __device__ __forceinline__ void ca_march(const DevGeom& G, const DevTables& Tb, 
       T pn[2], zn[2], wn[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        double sp = 0.0, sz = 0.0, sw = double(cur.w[u]);
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-          if constexpr (!REW) {
-            sp = __builtin_fma(ca[i], Y[i][u], sp);
-            sz = __builtin_fma(cb[i], Y[i][u], sz);
-          }
-          sw = __builtin_fma(cc[i], Y[i][u], sw);
-        }
+        const double sp = REW ? 0.0 : ca_dot(ca, Y, u, 0.0), sz = REW ? 0.0 : ca_dot(cb, Y, u, 0.0);
+        const double sw = ca_dot(cc, Y, u, double(cur.w[u]));
         pn[u] = static_cast<T>(sp);
         zn[u] = static_cast<T>(sz);
         wn[u] = static_cast<T>(sw);
         if constexpr (!REW) {
-          // ||p_{k+j}||^2, p_{k+j} = Y a_j: a_j lives on P_0..P_j, Z_0..Z_{j-1} (a_0 = e_0)
-          if (FAST || own[u]) {
-            acc[0] = __builtin_fma(Y[0][u], Y[0][u], acc[0]);
-#pragma unroll
-            for (int j = 1; j < S; ++j) {
-              double v = 0.0;
-#pragma unroll
-              for (int i = 0; i <= j; ++i) v = __builtin_fma(pa[j][i], Y[i][u], v);
-#pragma unroll
-              for (int i = 0; i < j; ++i) v = __builtin_fma(pa[j][S + 1 + i], Y[S + 1 + i][u], v);
-              acc[j] = __builtin_fma(v, v, acc[j]);
-            }
-          }
+          if (FAST || own[u]) ca_norms<S>(pa, Y, u, acc);
         }
       }
       if (FAST ? own_all : own_any) {
@@ -457,9 +478,6 @@ __device__ __forceinline__ void ca_march(const DevGeom& G, const DevTables& Tb, 
       if (m + q > mlast) return false;
       fetch(min(m + q + PF, mlast), buf[(q + PF) % NBUF]);
       core(qc, m + q, buf[q % NBUF]);
-#ifdef PMX_CA_SCHED_BARRIER
-      __builtin_amdgcn_sched_barrier(0);  // one row step at a time: bounded live ranges
-#endif
       return true;
     });
   }
@@ -469,14 +487,9 @@ __device__ __forceinline__ void ca_march(const DevGeom& G, const DevTables& Tb, 
   }
 }
 
-#ifndef PMX_CA_PF_GRAM
-#define PMX_CA_PF_GRAM 3
-#endif
-#ifndef PMX_CA_PF_UPD
-#define PMX_CA_PF_UPD 1
-#endif
-constexpr int kCaPfGram = PMX_CA_PF_GRAM, kCaPfUpd = PMX_CA_PF_UPD;
-
+// rows in flight (register prefetch): pass 1 (2 fields, compute-heavy) 3 rows ahead; pass 2 and the
+// fused producer (3 fields) 1
+constexpr int kCaPfGram = 3, kCaPfUpd = 1, kCaPfFuse = 1;
 
 // Which tiles a launch covers: the interior rectangle [ti_lo, ti_hi) x [tj_lo, tj_hi) of a pass's
 // tiling (every tile there is "fast": no Dirichlet node or partial width in reach), or the frame
@@ -555,12 +568,10 @@ k_ca_sweep(DevGeom G, DevTables Tb, T* w, T* z0, T* z1, T* p0, T* p1, double* __
   // pass 1's LDS-DMA row ring (4 slots of p, z rows, 2 KiB each)
   __shared__ double s_ring[(!UPD && DMA) ? 4 * 256 : 2];
   const unsigned* tbl = ctbl + int64_t(tj) * cwords;
-  const bool fast = PART == 1 || (j1 == j0 + Sh::WO - 1 && G.gi0 + i0 - S >= 1 && G.gi0 + i1 + S <= G.M - 1 &&
-                                   G.gj0 + j0 - Sh::HE >= 1 && G.gj0 + j0 - Sh::HE + 127 <= G.N - 1);
+  const bool fast = PART == 1 || ca_tile_fast(G, i0, i1, j0, j1, S, Sh::HE, Sh::WO);
   double acc[Sh::NQ];
 #pragma unroll
   for (int q = 0; q < Sh::NQ; ++q) acc[q] = 0.0;
-  // rows in flight: pass 1 (2 fields, compute-heavy) 3 rows ahead; pass 2 (3 fields) 1
   constexpr int PF = UPD ? kCaPfUpd : kCaPfGram;
 #define PMX_CA_MARCH(F, R) \
   ca_march<T, S, UPD, F, PF, R>(G, Tb, K, pin, zin, pout, zout, w, i0, i1, j0, j1, tbl, faces, acc, ca, cb, cc, pa)
@@ -628,7 +639,7 @@ struct CaFRow {
 // workgroup barrier per row step.  One wave holding both chains' register windows, the Gram sums and
 // the prefetch rows needs ~300 VGPRs (1 wave per SIMD, latency-bound: measured 1.38-2.3 ms/iteration
 // against 1.20 unfused at 16384^2); split, each wave holds half and the SIMDs keep 3 of them.
-template <typename T, int S, bool FAST, int PF, int ROLE, int RG = 1>
+template <typename T, int S, bool FAST, int PF, int ROLE>
 __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, const T* __restrict__ pin,
                                                const T* __restrict__ zin, T* __restrict__ pout, T* __restrict__ zout,
                                                T* __restrict__ w, int i0, int i1, int j0, int j1,
@@ -636,8 +647,7 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
                                                double (&acc)[CaShape<S>::NQ], double (&nacc)[S],
                                                const double (&ca)[CaShape<S>::NB], const double (&cb)[CaShape<S>::NB],
                                                const double (&cc)[CaShape<S>::NB],
-                                               const double (&pa)[S][CaShape<S>::NB], double* ring,
-                                               unsigned long long* tm = nullptr, double* dring = nullptr) {
+                                               const double (&pa)[S][CaShape<S>::NB], double* ring) {
   using Sh = CaShape<S>;
   constexpr int NB = Sh::NB, HE = CaFuseShape<S>::HE;
   const int64_t P = G.pitch;
@@ -654,42 +664,14 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
   const bool own_all = own[0] && own[1];
   const bool own_any = own[0] || own[1];
   auto interior_row = [&](int m) { return G.gi0 + m >= 1 && G.gi0 + m <= G.M - 1; };
-  // ring slot k: the new p row at ring + k * 256, z at + 128 (2 doubles per lane).  2 RG slots: the
-  // waves meet once per RG row steps (the producer after its group's last step, the consumer before
-  // its group's first), so one wave's slow row is absorbed by the other's group; step t = m - mfirst
-  // uses slot t mod 2 RG (rhi: the unrolled iteration's offset, for RG = 4)
-  static_assert(RG == 1 || RG == 2 || RG == 4, "ca_march_fused: 1, 2 or 4 row steps per barrier");
-  int rhi = 0;
-  auto slot_of = [&](auto qc) {
-    constexpr int q = decltype(qc)::value;
-    if constexpr (RG == 4) return rhi + q;
-    else return q & (2 * RG - 1);
-  };
+  // ring slot k: the new p row at ring + k * 256, z at + 128 (2 doubles per lane).  2 slots, one
+  // barrier per row step: step t = m - mfirst uses slot t & 1
   typedef double d2 __attribute__((ext_vector_type(2)));
-#ifdef PMX_CAF_TIMING  // study builds: s_memtime ticks a wave spends in the row barriers
-  unsigned long long t_sync = 0;
-  const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-  auto sync = [&] {
-    const unsigned long long a = __builtin_amdgcn_s_memtime();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    t_sync += __builtin_amdgcn_s_memtime() - a;
-  };
-  auto tdone = [&] {
-    if (tm) {
-      tm[0] = __builtin_amdgcn_s_memtime() - t_start;
-      tm[1] = t_sync;
-    }
-  };
-#else
   auto sync = [] {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   };
-  auto tdone = [] {};
-#endif
 
   // register windows as ca_march's: level l of a chain at row r in slot (r - mfirst) & 3.  The
   // producer's chain (block b's basis) trails the loaded row by l rows, the consumer's (block b+1's)
@@ -737,19 +719,6 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
       return true;
     });
   };
-  auto gather = [&](auto sc, double (&Y)[NB][2]) {
-    constexpr int sl = decltype(sc)::value;
-#pragma unroll
-    for (int l = 0; l <= S; ++l) {
-      Y[l][0] = XP[l][sl][0];
-      Y[l][1] = XP[l][sl][1];
-    }
-#pragma unroll
-    for (int l = 0; l < S; ++l) {
-      Y[S + 1 + l][0] = XZ[l][sl][0];
-      Y[S + 1 + l][1] = XZ[l][sl][1];
-    }
-  };
 
   if constexpr (ROLE == 0) {
     // ---- producer: rows mfirst .. mlast of (p_b, z_b); at step m the basis of row g1 = m - S is
@@ -776,20 +745,14 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
       const int g1 = m - S;
       if (g1 < i0 - S) return;
       double Y[NB][2];
-      gather(std::integral_constant<int, (q - S) & 3>{}, Y);
+      ca_gather<S, (q - S) & 3>(XP, XZ, Y);
       T pn[2], zn[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        double sp = 0.0, sz = 0.0;
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-          sp = __builtin_fma(ca[i], Y[i][u], sp);
-          sz = __builtin_fma(cb[i], Y[i][u], sz);
-        }
-        pn[u] = static_cast<T>(sp);
-        zn[u] = static_cast<T>(sz);
+        pn[u] = static_cast<T>(ca_dot(ca, Y, u, 0.0));
+        zn[u] = static_cast<T>(ca_dot(cb, Y, u, 0.0));
       }
-      double* sl = ring + slot_of(qc) * 256;
+      double* sl = ring + (q & 1) * 256;
       *reinterpret_cast<d2*>(sl + 2 * lane) = d2{double(pn[0]), double(pn[1])};
       *reinterpret_cast<d2*>(sl + 128 + 2 * lane) = d2{double(zn[0]), double(zn[1])};
       if (g1 < i0 || g1 > i1) return;
@@ -797,22 +760,8 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
       T wn[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        double sw = double(cur.w[u]);
-#pragma unroll
-        for (int i = 0; i < NB; ++i) sw = __builtin_fma(cc[i], Y[i][u], sw);
-        wn[u] = static_cast<T>(sw);
-        if (FAST || own[u]) {
-          nacc[0] = __builtin_fma(Y[0][u], Y[0][u], nacc[0]);
-#pragma unroll
-          for (int j = 1; j < S; ++j) {
-            double v = 0.0;
-#pragma unroll
-            for (int i = 0; i <= j; ++i) v = __builtin_fma(pa[j][i], Y[i][u], v);
-#pragma unroll
-            for (int i = 0; i < j; ++i) v = __builtin_fma(pa[j][S + 1 + i], Y[S + 1 + i][u], v);
-            nacc[j] = __builtin_fma(v, v, nacc[j]);
-          }
-        }
+        wn[u] = static_cast<T>(ca_dot(cc, Y, u, double(cur.w[u])));
+        if (FAST || own[u]) ca_norms<S>(pa, Y, u, nacc);
       }
       if (FAST ? own_all : own_any) {
         const int64_t o = int64_t(g1) * P;
@@ -821,83 +770,19 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
         ca_store2<T>(w + o, c0, wn, FAST || own_all, own);
       }
     };
-    static_assert(PF == 1 || PF == 3 || PF == 4, "ca_march_fused: prefetch depth 1 or 3 (registers), 4 (LDS-DMA)");
-    if constexpr (PF == 4) {
-      // LDS-DMA ring (fp64 FAST tiles): row mfirst + t of p, z (and w of row t - S) in slot t & 3, 4 rows
-      // ahead, no VGPR buffers.  global_load_lds_dwordx4 is invisible to hipcc, so the march counts
-      // vmcnt itself (as pcg1_march's DMA mode): before reading row m, the ops younger than its DMAs
-      // are the DMAs of rows m+1 .. m+3 (3 each) and the stores of the steps m-4 .. m-1 that stored
-      // (p, z, w of an owned row: 3 each).  Other vector ops (cut-row face loads) only add younger
-      // ops, and hipcc's own waits for them only drain more.
-      static_assert(FAST && sizeof(T) == 8, "ca_march_fused: LDS-DMA rows for fp64 FAST tiles");
-      constexpr int D = 4;
-      const unsigned voff = unsigned(c0 + 8) * 8u;  // bytes from row - 8 (ca_col's unsigned form)
-      const unsigned lds0 = unsigned(reinterpret_cast<uintptr_t>(dring));
-      auto dma_row = [&](int m, int slot) {
-        const unsigned l = lds0 + unsigned(slot) * 3072u;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot's previous ds_reads have returned
-        const int mc = min(max(m, 1 - F.gh), G.nx + F.gh);
-        const int wc = min(max(m - S, 1 - F.gh), G.nx + F.gh);
-        dma16(pin + int64_t(mc) * P - 8, voff, l);
-        dma16(zin + int64_t(mc) * P - 8, voff, l + 1024u);
-        dma16(w + int64_t(wc) * P - 8, voff, l + 2048u);
-      };
-      // step t stores iff its row t - S is owned
-      auto stores = [&](int t) { return t >= mfirst && t - S >= i0 && t - S <= i1 ? 1 : 0; };
-#pragma unroll
-      for (int q = 0; q < D; ++q) dma_row(min(mfirst + q, mlast), q);
-      bool more = true;
-      for (int m = mfirst; more && m <= mlast; m += 4) {
-        rhi = (m - mfirst) & 4;
-        more = static_for_while<4>([&](auto qc) {
-          constexpr int q = decltype(qc)::value;
-          const int mm = m + q;
-          if (mm > mlast) return false;
-          const int nst = stores(mm - 4) + stores(mm - 3) + stores(mm - 2) + stores(mm - 1);
-          switch (nst) {
-            case 0: wait_vmcnt<3 * (D - 1)>(); break;
-            case 1: wait_vmcnt<3 * (D - 1) + 3>(); break;
-            case 2: wait_vmcnt<3 * (D - 1) + 6>(); break;
-            case 3: wait_vmcnt<3 * (D - 1) + 9>(); break;
-            default: wait_vmcnt<3 * (D - 1) + 12>(); break;
-          }
-          const double* sl = dring + q * 384;
-          const d2 pv = *reinterpret_cast<const d2*>(sl + 2 * lane);
-          const d2 zv = *reinterpret_cast<const d2*>(sl + 128 + 2 * lane);
-          const d2 wv = *reinterpret_cast<const d2*>(sl + 256 + 2 * lane);
-          CaFRow<T> cur;
-          cur.p[0] = pv.x;
-          cur.p[1] = pv.y;
-          cur.z[0] = zv.x;
-          cur.z[1] = zv.y;
-          cur.w[0] = wv.x;
-          cur.w[1] = wv.y;
-          dma_row(min(mm + D, mlast), q);
-          core(qc, mm, cur);
-          if (q % RG == RG - 1 || mm == mlast) sync();
-          return true;
-        });
-      }
-      wait_vmcnt<0>();  // no DMA may land after the wave has moved on (its LDS is the next tile's)
-#pragma unroll
-      for (int j = 0; j < S; ++j) nacc[j] = own_all ? nacc[j] : 0.0;
-      tdone();
-      return;
-    }
+    static_assert(PF == 1 || PF == 3, "ca_march_fused: prefetch depth 1 or 3");
     constexpr int NBUF = PF + 1;
     CaFRow<T> buf[NBUF];
 #pragma unroll
     for (int q = 0; q < PF; ++q) fetch(min(mfirst + q, mlast), buf[q]);
     bool more = true;
     for (int m = mfirst; more && m <= mlast; m += 4) {
-      rhi = (m - mfirst) & 4;
       more = static_for_while<4>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
         if (m + q > mlast) return false;
         fetch(min(m + q + PF, mlast), buf[(q + PF) % NBUF]);
         core(qc, m + q, buf[q % NBUF]);
-        // the group's rows are in the ring; the consumer has read the slots the next group rewrites
-        if (q % RG == RG - 1 || m + q == mlast) sync();
+        sync();  // the row is in the ring; the consumer has read the slot the next step rewrites
         return true;
       });
     }
@@ -905,7 +790,6 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
 #pragma unroll
       for (int j = 0; j < S; ++j) nacc[j] = own_all ? nacc[j] : 0.0;
     }
-    tdone();
   } else {
     // ---- consumer: after the producer's step m, row g1 = m - S of the new (p, z) is in the ring: block
     // b+1's basis from it (exactly as pass 1 would build it from the stored values) and, S rows
@@ -915,7 +799,7 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
       const int g1 = m - S;
       if (g1 < i0 - S) return;
       constexpr int s1 = (q - S) & 3;
-      const double* sl = ring + slot_of(qc) * 256;
+      const double* sl = ring + (q & 1) * 256;
       const d2 pv = *reinterpret_cast<const d2*>(sl + 2 * lane);
       const d2 zv = *reinterpret_cast<const d2*>(sl + 128 + 2 * lane);
       ch[s1] = ca_row_cls(ctbl, g1);
@@ -928,7 +812,7 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
       if (g2 < i0) return;
       constexpr int s2 = (q - 2 * S) & 3;
       double Y2[NB][2];
-      gather(std::integral_constant<int, s2>{}, Y2);
+      ca_gather<S, s2>(XP, XZ, Y2);
       double d[2];
       ca_diag(ch[s2], g2, K, G, F, c0, cmax, d);
 #pragma unroll
@@ -941,11 +825,10 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
     };
     bool more = true;
     for (int m = mfirst; more && m <= mlast; m += 4) {
-      rhi = (m - mfirst) & 4;
       more = static_for_while<4>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
         if (m + q > mlast) return false;
-        if (q % RG == 0) sync();
+        sync();
         core(qc, m + q);
         return true;
       });
@@ -954,20 +837,15 @@ __device__ __forceinline__ void ca_march_fused(const DevGeom& G, const CaK& K, c
 #pragma unroll
       for (int q = 0; q < Sh::NQ; ++q) acc[q] = own_all ? acc[q] : 0.0;
     }
-    tdone();
   }
 }
-
-#ifndef PMX_CA_PF_FUSE
-#define PMX_CA_PF_FUSE 1
-#endif
 
 // The fused pass (see ca_march_fused): one workgroup of two waves per tile.  After the reduction of
 // block b (CaState::nupd > 0) it applies block b and sums block b+1's Gram products; after a reduction
 // that stopped inside block b - 1 (nupd < 0) wave 0 rewinds w, as pass 2 would.  Partials: the Gram
 // products q at [q][tile] (wave 1), block b's norms j at NQ * ntiles + [j][tile] (wave 0): the
 // reduction's n = n2 = ntiles.
-template <typename T, int S, int MW, int PART, int RG, bool DMAF = false>
+template <typename T, int S, int MW, int PART>
 __global__ void __launch_bounds__(128, MW)
 k_ca_fused(DevGeom G, T* w, T* z0, T* z1, T* p0, T* p1, double* __restrict__ partials, const CaState* C, int TI,
            int tiles_j, const unsigned* __restrict__ ctbl, int cwords, CaFaces faces, CaPart part, int ntiles) {
@@ -1002,6 +880,9 @@ k_ca_fused(DevGeom G, T* w, T* z0, T* z1, T* p0, T* p1, double* __restrict__ par
   const CaK K = ca_consts(G);
   const int lane = threadIdx.x & 63;
   const unsigned* tbl = ctbl + int64_t(tj) * cwords;
+  // ca_tile_fast(G, i0, i1, j0, j1, 2 * S, Fs::HE, Fs::WO), spelled out: the call changes the SGPR spill
+  // counts of the general kernels (S = 3: 109 -> 107 in fp64, 126 -> 130 in fp32); make_ca_tiles checks
+  // the interior rectangle against ca_tile_fast
   const bool fast = PART == 1 || (j1 == j0 + Fs::WO - 1 && G.gi0 + i0 - 2 * S >= 1 && G.gi0 + i1 + 2 * S <= G.M - 1 &&
                                    G.gj0 + j0 - Fs::HE >= 1 && G.gj0 + j0 - Fs::HE + 127 <= G.N - 1);
   double acc[Sh::NQ], nacc[S];
@@ -1020,20 +901,12 @@ k_ca_fused(DevGeom G, T* w, T* z0, T* z1, T* p0, T* p1, double* __restrict__ par
                                                              j1, tbl, faces, acc, ca, cb, cc, pz);
     return;
   }
-  __shared__ double ring[2 * RG * 256];
-  // the producer's LDS-DMA rows (DMAF: fp64 interior tiles): 4 slots of p, z, w rows
-  __shared__ double dring[DMAF ? 4 * 384 : 2];
-  static_assert(!DMAF || (PART == 1 && sizeof(T) == 8), "k_ca_fused: LDS-DMA rows for fp64 interior tiles");
-  constexpr int PF = PMX_CA_PF_FUSE;
-  unsigned long long tm[2] = {0, 0};
-#define PMX_CAF_MARCH(FA, R)                                                                                        \
-  ca_march_fused<T, S, FA, PF, R, RG>(G, K, pin, zin, pout, zout, w, i0, i1, j0, j1, tbl, faces, acc, nacc, ca, cb, \
-                                      cc, pa, ring, tm)
+  __shared__ double ring[2 * 256];
+#define PMX_CAF_MARCH(FA, R)                                                                                       \
+  ca_march_fused<T, S, FA, kCaPfFuse, R>(G, K, pin, zin, pout, zout, w, i0, i1, j0, j1, tbl, faces, acc, nacc, ca, \
+                                         cb, cc, pa, ring)
   if (role == 0) {
-    if constexpr (DMAF)
-      ca_march_fused<T, S, true, 4, 0, RG>(G, K, pin, zin, pout, zout, w, i0, i1, j0, j1, tbl, faces, acc, nacc, ca, cb,
-                                           cc, pa, ring, tm, dring);
-    else if (PART == 1 || fast) PMX_CAF_MARCH(true, 0);
+    if (PART == 1 || fast) PMX_CAF_MARCH(true, 0);
     else if constexpr (PART != 1) PMX_CAF_MARCH(false, 0);
 #pragma unroll
     for (int j = 0; j + 1 < S; j += 2) wave_sum2_mfma(nacc[j], nacc[j + 1]);
@@ -1054,10 +927,6 @@ k_ca_fused(DevGeom G, T* w, T* z0, T* z1, T* p0, T* p1, double* __restrict__ par
     }
   }
 #undef PMX_CAF_MARCH
-#ifdef PMX_CAF_TIMING
-  if (lane == 0 && blk == 7 && id % 499 == 0)
-    printf("caf part %d role %d tile %d fast %d total %llu sync %llu\n", PART, role, id, int(fast), tm[0], tm[1]);
-#endif
 }
 
 // Row classes of every tile column (one thread per 16-row word): 2 bits per local row, over the
@@ -1551,14 +1420,14 @@ CaTiles make_ca_tiles(const DevGeom& G, int s, int rows, int rows2, int rows_f) 
   PMX_CHECK(rows2 >= 1 && rows2 <= 4096, "s-step PCG: pass-2 tile rows must be in [1, 4096]");
   t.rows2 = rows2;
   t.tiles_i2 = (G.nx + rows2 - 1) / rows2;
-  // interior rectangles (k_ca_sweep's `fast`): rows i0 - s .. i1 + s and columns j0 - he .. j0 - he + 127
+  // interior rectangles (ca_tile_fast): rows i0 - s .. i1 + s and columns j0 - he .. j0 - he + 127
   // strictly inside the grid, full width.  i0 = 1 + ti rows: ti >= 1 and (ti + 1) rows <= nx - s; j0 = 1 +
-  // tj wo: tj >= 1 and tj wo + 128 - he <= ny.  Checked tile by tile against the kernel's condition.
-  auto fast = [&](int ti, int tj, int r) {
-    const int i0 = 1 + ti * r, i1 = std::min(i0 + r - 1, G.nx);
-    const int j0 = 1 + tj * t.wo, j1 = std::min(j0 + t.wo - 1, G.ny);
-    return j1 == j0 + t.wo - 1 && G.gi0 + i0 - s >= 1 && G.gi0 + i1 + s <= G.M - 1 && G.gj0 + j0 - t.he >= 1 &&
-           G.gj0 + j0 - t.he + 127 <= G.N - 1;
+  // tj wo: tj >= 1 and tj wo + 128 - he <= ny.  Checked tile by tile against the kernels' condition.
+  // tile (ti, tj) of a tiling of `rows` x wo tiles, placed as the kernels place it; r: the march's radius
+  auto fast = [&](int ti, int tj, int rows, int r, int he, int wo) {
+    const int i0 = 1 + ti * rows, i1 = std::min(i0 + rows - 1, G.nx);
+    const int j0 = 1 + tj * wo, j1 = std::min(j0 + wo - 1, G.ny);
+    return ca_tile_fast(G, i0, i1, j0, j1, r, he, wo);
   };
   t.tj_lo = std::min(1, t.tiles_j);
   t.tj_hi = std::max(t.tj_lo, std::min(t.tiles_j, (G.ny - 128 + t.he) / t.wo + 1));
@@ -1571,12 +1440,11 @@ CaTiles make_ca_tiles(const DevGeom& G, int s, int rows, int rows2, int rows_f) 
     for (int ti = 0; ti < tiles_i; ++ti)
       for (int tj = 0; tj < t.tiles_j; ++tj) {
         const bool in = ti >= lo && ti < hi && tj >= t.tj_lo && tj < t.tj_hi;
-        PMX_CHECK(!in || fast(ti, tj, r), "s-step PCG: interior tile (" << ti << ", " << tj << ") is not fast");
+        PMX_CHECK(!in || fast(ti, tj, r, s, t.he, t.wo), "s-step PCG: interior tile (" << ti << ", " << tj << ") is not fast");
       }
   };
   rect(rows, t.tiles_i, t.ti_lo, t.ti_hi);
-  rect(rows2, t.tiles_i2, t.ti_lo2, t.ti_hi2);
-  if (t.ti_hi <= t.ti_lo || t.ti_hi2 <= t.ti_lo2) t.split = t.split_upd = 0;
+  if (t.ti_hi <= t.ti_lo) t.split = 0;
   // rows up to nx + 2s (the fused march's lowest loaded row), 16 per word from row -kCaRowOff
   t.cwords = (G.nx + 4 * s + 2 * kCaRowOff + 15) / 16 + 1;
   // the fused tiling: radius 2s (he_f = 2s columns per side), rows_f rows.  Auto: 64 (16384^2 at 3
@@ -1602,12 +1470,6 @@ CaTiles make_ca_tiles(const DevGeom& G, int s, int rows, int rows2, int rows_f) 
   t.tiles_i_f = (G.nx + rows_f - 1) / rows_f;
   {
     const int r = 2 * s;  // the fused kernel's radius
-    auto fastf = [&](int ti, int tj) {
-      const int i0 = 1 + ti * rows_f, i1 = std::min(i0 + rows_f - 1, G.nx);
-      const int j0 = 1 + tj * t.wo_f, j1 = std::min(j0 + t.wo_f - 1, G.ny);
-      return j1 == j0 + t.wo_f - 1 && G.gi0 + i0 - r >= 1 && G.gi0 + i1 + r <= G.M - 1 && G.gj0 + j0 - t.he_f >= 1 &&
-             G.gj0 + j0 - t.he_f + 127 <= G.N - 1;
-    };
     t.tj_lo_f = std::min(1, t.tiles_j_f);
     t.tj_hi_f = std::max(t.tj_lo_f, std::min(t.tiles_j_f, (G.ny - 128 + t.he_f) / t.wo_f + 1));
     t.ti_lo_f = std::min((r + rows_f - 1) / rows_f, t.tiles_i_f);  // i0 - r >= 1
@@ -1618,7 +1480,7 @@ CaTiles make_ca_tiles(const DevGeom& G, int s, int rows, int rows2, int rows_f) 
     }
     for (int ti = t.ti_lo_f; ti < t.ti_hi_f; ++ti)
       for (int tj = t.tj_lo_f; tj < t.tj_hi_f; ++tj)
-        PMX_CHECK(fastf(ti, tj), "s-step PCG: interior fused tile (" << ti << ", " << tj << ") is not fast");
+        PMX_CHECK(fast(ti, tj, rows_f, r, t.he_f, t.wo_f), "s-step PCG: interior fused tile (" << ti << ", " << tj << ") is not fast");
   }
   return t;
 }
@@ -1658,45 +1520,38 @@ void launch_ca_sweep(const DevGeom& G, const DevTables& Tb, T* w, T* z0, T* z1, 
   const int n = upd ? t.ntiles2() : t.ntiles();
   const int rows = upd ? t.rows2 : t.rows;
   const int64_t pbase = upd ? int64_t(ca_nq(t.s) - t.s) * t.ntiles() : 0;  // norms after the Gram products
-  const int ti_lo = upd ? t.ti_lo2 : t.ti_lo, ti_hi = upd ? t.ti_hi2 : t.ti_hi;
-  const int tiles_i = upd ? t.tiles_i2 : t.tiles_i;
-  const int nin = (ti_hi - ti_lo) * (t.tj_hi - t.tj_lo);
+  const int nin = (t.ti_hi - t.ti_lo) * (t.tj_hi - t.tj_lo);
   const CaFaces F{t.fa, t.fb, t.gh};
-  const CaPart P1{1, tiles_i, ti_lo, ti_hi, t.tj_lo, t.tj_hi}, P2{2, tiles_i, ti_lo, ti_hi, t.tj_lo, t.tj_hi},
-      P0{0, tiles_i, 0, 0, 0, 0};
-#define PMX_CA_K(SS, U, MW, D, PT, PP, NB)                                                                          \
-  do {                                                                                                              \
-    if ((NB) > 0)                                                                                                   \
-      hipLaunchKernelGGL((k_ca_sweep<T, SS, U, MW, (D) && sizeof(T) == 8, PT>), dim3(NB), dim3(64), 0,            \
-                         (PT) == 2 ? sframe : s, G, Tb, w,                                                           \
-                         z0, z1, p0, p1, partials, S, C, rows, t.tiles_j, t.tbl, t.cwords, pbase, F, PP, n);        \
+  const CaPart P1{1, t.tiles_i, t.ti_lo, t.ti_hi, t.tj_lo, t.tj_hi}, P2{2, t.tiles_i, t.ti_lo, t.ti_hi, t.tj_lo, t.tj_hi},
+      P0{0, upd ? t.tiles_i2 : t.tiles_i, 0, 0, 0, 0};
+  // D: LDS-DMA rows, fp64 only (no such kernel is instantiated for float)
+#define PMX_CA_K(SS, U, MW, D, PT, PP, NB)                                                                      \
+  do {                                                                                                          \
+    if constexpr (!(D) || sizeof(T) == 8) {                                                                     \
+      if ((NB) > 0)                                                                                             \
+        hipLaunchKernelGGL((k_ca_sweep<T, SS, U, MW, D, PT>), dim3(NB), dim3(64), 0, (PT) == 2 ? sframe : s, G, \
+                           Tb, w, z0, z1, p0, p1, partials, S, C, rows, t.tiles_j, t.tbl, t.cwords, pbase, F, PP, n); \
+    }                                                                                                           \
   } while (0)
-  // split (default): the interior tiles with the fast-only kernel at 3 waves per SIMD, the frame with
-  // the general one at 2; else every tile general at waves_gram / waves_upd
+  // pass 1 split (default): the interior tiles with the fast-only kernel (3 waves per SIMD with LDS-DMA
+  // rows; register rows would spill there: 2), the frame with the general one at 2; else every tile
+  // general at 2.  Pass 2: one general kernel at 3.
   // the tiles that read ghost rows -- the frame on sframe, or every tile on s -- wait for frame_wait
-  const bool split = (upd ? t.split_upd : t.split) && nin > 0;
+  const bool split = !upd && t.split && nin > 0;
   if (frame_wait) HIP_CHECK(hipStreamWaitEvent(split ? sframe : s, frame_wait, 0));
-#define PMX_CA(SS)                                                                                                   \
-  do {                                                                                                               \
-    if (split) {                                                                                                     \
-      if (upd) {                                                                                                     \
-        PMX_CA_K(SS, true, 2, false, 2, P2, n - nin);                                                                \
-        PMX_CA_K(SS, true, 3, false, 1, P1, nin);                                                                    \
-      } else {                                                                                                       \
-        PMX_CA_K(SS, false, 2, false, 2, P2, n - nin);                                                               \
-        if (t.dma) PMX_CA_K(SS, false, 3, true, 1, P1, nin);                                                         \
-        else PMX_CA_K(SS, false, 2, false, 1, P1, nin); /* register rows: 3 waves would spill */                     \
-      }                                                                                                              \
-    } else if (upd) {                                                                                                \
-      if (t.waves_upd == 2) PMX_CA_K(SS, true, 2, false, 0, P0, n);                                                  \
-      else PMX_CA_K(SS, true, 3, false, 0, P0, n);                                                                   \
-    } else if (t.dma) {                                                                                              \
-      if (t.waves_gram == 3) PMX_CA_K(SS, false, 3, true, 0, P0, n);                                                 \
-      else PMX_CA_K(SS, false, 2, true, 0, P0, n);                                                                   \
-    } else {                                                                                                         \
-      if (t.waves_gram == 3) PMX_CA_K(SS, false, 3, false, 0, P0, n);                                                \
-      else PMX_CA_K(SS, false, 2, false, 0, P0, n);                                                                  \
-    }                                                                                                                \
+#define PMX_CA(SS)                                          \
+  do {                                                      \
+    if (upd) {                                              \
+      PMX_CA_K(SS, true, 3, false, 0, P0, n);               \
+    } else if (split) {                                     \
+      PMX_CA_K(SS, false, 2, false, 2, P2, n - nin);        \
+      if (t.dma) PMX_CA_K(SS, false, 3, true, 1, P1, nin);  \
+      else PMX_CA_K(SS, false, 2, false, 1, P1, nin);       \
+    } else if (t.dma) {                                     \
+      PMX_CA_K(SS, false, 2, true, 0, P0, n);               \
+    } else {                                                \
+      PMX_CA_K(SS, false, 2, false, 0, P0, n);              \
+    }                                                       \
   } while (0)
   if (t.s == 2) PMX_CA(2);
   else PMX_CA(3);
@@ -1717,38 +1572,29 @@ void launch_ca_fused(const DevGeom& G, T* w, T* z0, T* z1, T* p0, T* p1, double*
   const CaFaces F{t.fa, t.fb, t.gh};
   const CaPart P1{1, t.tiles_i_f, t.ti_lo_f, t.ti_hi_f, t.tj_lo_f, t.tj_hi_f},
       P2{2, t.tiles_i_f, t.ti_lo_f, t.ti_hi_f, t.tj_lo_f, t.tj_hi_f}, P0{0, t.tiles_i_f, 0, 0, 0, 0};
-#define PMX_CAF_KD(SS, MW, PT, PP, NB, RG, DM)                                                                     \
-  do {                                                                                                              \
-    if ((NB) > 0)                                                                                                   \
-      hipLaunchKernelGGL((k_ca_fused<T, SS, MW, PT, RG, DM>), dim3(NB), dim3(128), 0, (PT) == 2 ? sframe : s, G, w, \
-                         z0, z1, p0, p1, partials, C, t.rows_f, t.tiles_j_f, t.tbl_f, t.cwords, F, PP, n);          \
+#define PMX_CAF_K(SS, MW, PT, PP, NB)                                                                           \
+  do {                                                                                                          \
+    if ((NB) > 0)                                                                                               \
+      hipLaunchKernelGGL((k_ca_fused<T, SS, MW, PT>), dim3(NB), dim3(128), 0, (PT) == 2 ? sframe : s, G, w, z0, \
+                         z1, p0, p1, partials, C, t.rows_f, t.tiles_j_f, t.tbl_f, t.cwords, F, PP, n);          \
   } while (0)
-#define PMX_CAF_K(SS, MW, PT, PP, NB, RG) PMX_CAF_KD(SS, MW, PT, PP, NB, RG, false)
-  constexpr bool kDmaOk = sizeof(T) == 8;
   const bool split = t.split_f && nin > 0;
   if (frame_wait) HIP_CHECK(hipStreamWaitEvent(split ? sframe : s, frame_wait, 0));
-  // interior kernel: rows per barrier group (rg_f), 3 waves per SIMD (2: RG 1 only)
-#define PMX_CAF(SS)                                                 \
-  do {                                                              \
-    if (split) {                                                    \
-      if (t.frame_first_f) PMX_CAF_K(SS, 2, 2, P2, n - nin, 1);     \
-      if (t.waves_f == 2) PMX_CAF_K(SS, 2, 1, P1, nin, 1);          \
-      else if (t.rg_f == 4) PMX_CAF_K(SS, 3, 1, P1, nin, 4);        \
-      else if (t.rg_f == 2) PMX_CAF_K(SS, 3, 1, P1, nin, 2);        \
-      else if (kDmaOk && t.dma_f) PMX_CAF_KD(SS, 3, 1, P1, nin, 1, kDmaOk); \
-      else PMX_CAF_K(SS, 3, 1, P1, nin, 1);                         \
-      if (!t.frame_first_f) PMX_CAF_K(SS, 2, 2, P2, n - nin, 1);    \
-    } else if (t.waves_f == 3) {                                    \
-      PMX_CAF_K(SS, 3, 0, P0, n, 1);                                \
-    } else {                                                        \
-      PMX_CAF_K(SS, 2, 0, P0, n, 1);                                \
-    }                                                               \
+  // split: the interior kernel (3 waves per SIMD) launched first, then the frame (in a captured graph
+  // the first-launched node starts first); else every tile by the general kernel
+#define PMX_CAF(SS)                        \
+  do {                                     \
+    if (split) {                           \
+      PMX_CAF_K(SS, 3, 1, P1, nin);        \
+      PMX_CAF_K(SS, 2, 2, P2, n - nin);    \
+    } else {                               \
+      PMX_CAF_K(SS, 3, 0, P0, n);          \
+    }                                      \
   } while (0)
   if (t.s == 2) PMX_CAF(2);
   else PMX_CAF(3);
 #undef PMX_CAF
 #undef PMX_CAF_K
-#undef PMX_CAF_KD
   HIP_CHECK(hipGetLastError());
 }
 

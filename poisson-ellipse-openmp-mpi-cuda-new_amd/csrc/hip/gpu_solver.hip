@@ -163,7 +163,6 @@ GpuOptions resolve_options(const GpuOptions& in) {
   PMX_CHECK(o.ca_rows >= 0 && o.ca_rows <= 4096, "s-step PCG: tile rows must be 0 (auto) .. 4096");
   env_int("PMX_CA_DMA", o.ca_dma);
   env_int("PMX_CA_SPLIT", o.ca_split);
-  env_int("PMX_CA_SPLIT_UPD", o.ca_split_upd);
   env_int("PMX_CA_FRAME_STREAM", o.ca_frame_stream);
   env_int("PMX_CA_FUSE", o.ca_fuse);
   env_int("PMX_CA_ROWS_F", o.ca_rows_f);
@@ -175,12 +174,7 @@ GpuOptions resolve_options(const GpuOptions& in) {
   env_int("PMX_PCG1_SPLIT", o.split_sweep);
   PMX_CHECK(o.split_sweep >= -1 && o.split_sweep <= 1, "split_sweep must be -1, 0 or 1");
   PMX_CHECK(o.ca_split >= -1 && o.ca_split <= 1, "s-step PCG: ca_split must be -1, 0 or 1");
-  PMX_CHECK(o.ca_split_upd >= -1 && o.ca_split_upd <= 1, "s-step PCG: ca_split_upd must be -1, 0 or 1");
-  env_int("PMX_CA_WAVES_GRAM", o.ca_waves_gram);
-  env_int("PMX_CA_WAVES_UPD", o.ca_waves_upd);
   PMX_CHECK(o.ca_dma >= -1 && o.ca_dma <= 1, "s-step PCG: ca_dma must be -1, 0 or 1");
-  PMX_CHECK((o.ca_waves_gram == 2 || o.ca_waves_gram == 3) && (o.ca_waves_upd == 2 || o.ca_waves_upd == 3),
-            "s-step PCG: waves per SIMD must be 2 or 3");
   env_int("PMX_PCG1_DMA", o.dma1);
   env_int("PMX_PCG1_DMA_W", o.dma1w);
   PMX_CHECK(o.dma1 == 0 || o.dma1 == 2 || o.dma1 == 3, "pcg1 LDS-DMA prefetch depth must be 0, 2 or 3");
@@ -447,15 +441,7 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
     r2_ = field_raw(4);  // the second z buffer
     ca_tiles_ = make_ca_tiles(ca_geom_, opt_.ca_s, opt_.ca_rows, opt_.ca_rows2, opt_.ca_rows_f);
     ca_tiles_.fuse = ca_fuse_ ? 1 : 0;
-    if (const char* e = study_env("PMX_CA_WAVES_F"); e && e[0]) ca_tiles_.waves_f = std::atoi(e);
     if (const char* e = study_env("PMX_CA_SPLIT_F"); e && e[0]) ca_tiles_.split_f = std::atoi(e);
-    if (const char* e = study_env("PMX_CA_RG_F"); e && e[0]) ca_tiles_.rg_f = std::atoi(e);
-    if (const char* e = study_env("PMX_CA_DMA_F"); e && e[0]) ca_tiles_.dma_f = std::atoi(e);
-    if (const char* e = study_env("PMX_CA_FRAME_FIRST_F"); e && e[0]) ca_tiles_.frame_first_f = std::atoi(e);
-    PMX_CHECK(ca_tiles_.dma_f == 0 || ca_tiles_.dma_f == 1, "s-step PCG: fused LDS-DMA rows must be 0 or 1");
-    PMX_CHECK(ca_tiles_.rg_f == 1 || ca_tiles_.rg_f == 2 || ca_tiles_.rg_f == 4,
-              "s-step PCG: fused row steps per barrier must be 1, 2 or 4");
-    PMX_CHECK(ca_tiles_.waves_f == 2 || ca_tiles_.waves_f == 3, "s-step PCG: fused waves per SIMD must be 2 or 3");
     // the face coefficients of every node, read on the rows the ellipse cuts (2 more field-sized arrays)
     // fp64 whatever the fields' storage, in the fields' pitch (elements); column 1 of every row 256-B aligned
     const size_t face_off = size_t(gh_ - 1) * size_t(geom_.pitch) + 31;
@@ -467,16 +453,12 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
     ca_build_faces(ca_geom_, ca_tables_, const_cast<double*>(ca_tiles_.fa), const_cast<double*>(ca_tiles_.fb), ca_gh_, nullptr);
     const bool split = opt_.ca_split == -1 ? geom_.nb != 0 : opt_.ca_split == 1;  // see GpuOptions::ca_split
     if (!split) ca_tiles_.split = 0;
-    if (!(opt_.ca_split_upd == -1 ? split : opt_.ca_split_upd == 1)) ca_tiles_.split_upd = 0;
-    if (!ca_tiles_.split) ca_tiles_.split_upd = ca_tiles_.split_upd && opt_.ca_split_upd == 1;
     ca_tiles_.dma = elem_ == 8 ? (opt_.ca_dma == -1 ? int(split) : opt_.ca_dma) : 0;  // LDS-DMA rows: fp64
     if (ca_tiles_.split && opt_.ca_frame_stream) {
       HIP_CHECK(hipStreamCreateWithFlags(&ca_side_, hipStreamNonBlocking));
       HIP_CHECK(hipEventCreateWithFlags(&ca_ev_fork_, hipEventDisableTiming));
       HIP_CHECK(hipEventCreateWithFlags(&ca_ev_join_, hipEventDisableTiming));
     }
-    ca_tiles_.waves_gram = opt_.ca_waves_gram;
-    ca_tiles_.waves_upd = opt_.ca_waves_upd;
     HIP_CHECK(hipMalloc(&ca_tbl_, size_t(ca_tiles_.tiles_j) * ca_tiles_.cwords * sizeof(unsigned)));
     ca_tiles_.tbl = ca_tbl_;
     ca_build_classes(ca_geom_, ca_tables_, ca_tiles_, ca_tbl_, nullptr);

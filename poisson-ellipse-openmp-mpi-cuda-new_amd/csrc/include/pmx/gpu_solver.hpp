@@ -76,22 +76,19 @@ struct GpuOptions {
   int algo = -1;
   // s-step PCG: block size (2 or 3) and tile height (0 = auto).  PMX_CA_S / PMX_CA_ROWS.
   int ca_s = 3, ca_rows = 0, ca_rows2 = 0;  // (ca_rows2: pass 2's tile rows, PMX_CA_ROWS_UPD)
-  // s-step pass shapes: pass 1 rows by LDS-DMA (1) or registers (0); waves per SIMD each pass's
-  // registers must allow (2 or 3).  PMX_CA_DMA / PMX_CA_WAVES_GRAM / PMX_CA_WAVES_UPD.  Same-process
-  // A/B at 16384^2 (profiles/r5/ca/): pass 1 1712 us with registers vs 1815 with LDS-DMA, 2407 at 3
-  // waves (spills); pass 2 3025 at 2 waves vs 3105 at 3 (56 B of spills) -- within noise
+  // s-step pass 1: rows by LDS-DMA (1) or registers (0).  PMX_CA_DMA.  Same-process A/B at 16384^2
+  // with one general kernel (profiles/r5/ca/): 1712 us with registers vs 1815 with LDS-DMA.
   // ca_dma -1: LDS-DMA rows with the split kernels (below), registers without
-  int ca_dma = -1, ca_waves_gram = 2, ca_waves_upd = 3;
-  // s-step: the interior tiles of a pass by a kernel without the Dirichlet / partial-tile paths, whose
-  // registers fit 3 waves per SIMD (pass 1 with LDS-DMA rows), the frame by the general kernel on a
-  // side stream (1), or every tile by the general kernel (0); -1 = split on row strips only.
-  // PMX_CA_SPLIT / PMX_CA_SPLIT_UPD (pass 2; -1: as pass 1).  16384^2, every session on the fastest
-  // of 20 probed blocks, 5 same-process rounds: 1169 us/iteration with pass 1 split and pass 2 one
-  // kernel, 1178 both split, 1222 neither (profiles/r5/ca/split/placed_ab16384.log; without the probe
-  // the placement lottery hid the difference).  On row strips pass 1's frame tiles also wait for the
-  // ghost exchange while its interior runs.
+  int ca_dma = -1;
+  // s-step: the interior tiles of pass 1 by a kernel without the Dirichlet / partial-tile paths, whose
+  // registers fit 3 waves per SIMD (with LDS-DMA rows), the frame by the general kernel on a side
+  // stream (1), or every tile by the general kernel (0); -1 = split on row strips only.  PMX_CA_SPLIT.
+  // Pass 2 is one general kernel.  16384^2, every session on the fastest of 20 probed blocks, 5
+  // same-process rounds: 1169 us/iteration with pass 1 split, 1222 without
+  // (profiles/r5/ca/split/placed_ab16384.log; without the probe the placement lottery hid the
+  // difference).  On row strips pass 1's frame tiles also wait for the ghost exchange while its
+  // interior runs.
   int ca_split = 1;
-  int ca_split_upd = 0;
   // ... the frame kernel on a side stream, overlapping the interior (1), or after it (0).  PMX_CA_FRAME_STREAM.
   int ca_frame_stream = 1;
   // s-step: pass 2 of block b and pass 1 of block b+1 as ONE fused pass (k_ca_fused, 48 instead of 64
@@ -175,7 +172,7 @@ inline const char* dtype_name(const GpuOptions& o) {
 // variable cannot change what a run or a test measures.
 GpuOptions resolve_options(const GpuOptions& opt);
 // getenv(name) in study mode, nullptr otherwise (driver-level study knobs: PMX_DIRECT_ROWS,
-// PMX_PCG1_SPLIT, PMX_FRAME_ON_COMM, PMX_FORK_ONE_QUEUE, PMX_CA_WAVES_F, PMX_CA_SPLIT_F)
+// PMX_PCG1_SPLIT, PMX_FRAME_ON_COMM, PMX_FORK_ONE_QUEUE, PMX_CA_SPLIT_F)
 const char* study_env(const char* name);
 // Single-pass (pcg1) or two-sweep (pcg2) iteration for this problem/process grid/options.  A pure
 // function of global data (see GpuOptions::algo); `device_total_bytes` = 0 skips the size test.

@@ -146,28 +146,17 @@ struct CaTiles {
   const double* fa = nullptr;  // face coefficients a, b at every local node (ca_build_faces), pitched as
   const double* fb = nullptr;  // the fields, local (0, 0); read on the rows the ellipse cuts
   int gh = 2;                  // ghost rows of the fields on each side: 2, or 3 = s on a decomposed strip
-  // interior rectangles of the two tilings (every tile "fast": no Dirichlet node or partial width in
-  // reach): [ti_lo, ti_hi) x [tj_lo, tj_hi) for pass 1, [ti_lo2, ti_hi2) x (same columns) for pass 2
-  int ti_lo = 0, ti_hi = 0, tj_lo = 0, tj_hi = 0, ti_lo2 = 0, ti_hi2 = 0;
-  int split = 1;       // interior tiles by a fast-only kernel at 3 waves per SIMD, the frame by the general one
-  int split_upd = 1;   // the same for pass 2
+  // pass 1's interior rectangle (every tile "fast": no Dirichlet node or partial width in reach):
+  // [ti_lo, ti_hi) x [tj_lo, tj_hi); pass 2 runs every tile with one general kernel
+  int ti_lo = 0, ti_hi = 0, tj_lo = 0, tj_hi = 0;
+  int split = 1;       // pass 1: interior tiles by a fast-only kernel at 3 waves per SIMD, the frame by the general one
   int dma = 1;         // pass 1: interior tiles prefetch their rows by LDS-DMA (0: registers)
-  int waves_gram = 2;  // waves per SIMD the pass-1 registers must allow (2 or 3)
-  int waves_upd = 3;   // ... pass 2 (2 or 3)
   // fused pass (k_ca_fused: pass 2 of block b + pass 1 of block b+1 in one march, radius 2s): its own
   // tiling of rows_f x wo_f (= 128 - 4 s) tiles, its interior rectangle and its row-class table
   int fuse = 0;
   int rows_f = 0, tiles_i_f = 0, tiles_j_f = 0, wo_f = 116, he_f = 6;
   int ti_lo_f = 0, ti_hi_f = 0, tj_lo_f = 0, tj_hi_f = 0;
-  int split_f = 1;     // interior tiles by the fast-only kernel, the frame by the general one
-  int waves_f = 3;     // waves per SIMD the fused interior kernel's registers must allow (2 or 3)
-  int rg_f = 1;        // fused interior tiles: row steps per producer / consumer barrier (1, 2, 4)
-  // split fused pass: the frame kernel launched before (1) or after (0) the interior.  In a captured
-  // graph the first-launched node starts first: frame first delayed the interior by up to ~140 us and
-  // ran it slower; driver command 1.004-1.013 (frame first) vs 0.965-0.970 ms/step (frame last), three
-  // interleaved fresh-process runs each (profiles/r6/frame_order/)
-  int frame_first_f = 0;
-  int dma_f = 0;       // fp64 fused interior tiles: the producer's rows by LDS-DMA, 4 ahead (0: registers, 1 ahead)
+  int split_f = 1;     // interior tiles by the fast-only kernel (launched first), the frame by the general one
   unsigned* tbl_f = nullptr;
   int ntiles() const { return tiles_i * tiles_j; }
   int ntiles2() const { return tiles_i2 * tiles_j; }
