@@ -8,7 +8,9 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cmath>
 #include <cstring>
+#include <string>
 
 #include "pmx/common.hpp"
 #include "pmx/cpu_pcg.hpp"
@@ -28,6 +30,38 @@ py::array_t<double> to_numpy(const std::vector<double>& v, std::vector<py::ssize
   py::array_t<double> a(shape);
   std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(double));
   return a;
+}
+
+// An optional global field argument (rhs, w0): None, a NumPy array or a CPU torch tensor of
+// (M+1) x (N+1) float64 values.  ValueError -- before anything is uploaded -- for any other type,
+// dtype or shape, for a device tensor and for non-finite values.
+struct FieldArg {
+  py::array_t<double, py::array::c_style> arr;  // owns (or shares) the data `ptr` points to
+  const double* ptr = nullptr;
+};
+FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::string& name) {
+  FieldArg f;
+  if (obj.is_none()) return f;
+  py::object a = obj;
+  if (py::hasattr(a, "numpy") && py::hasattr(a, "device")) {  // a torch tensor
+    if (a.attr("device").attr("type").cast<std::string>() != "cpu")
+      throw py::value_error(name + ": device tensors are not supported, pass a NumPy array or a CPU tensor");
+    a = a.attr("detach")().attr("numpy")();
+  }
+  if (!py::isinstance<py::array>(a)) throw py::value_error(name + " must be a NumPy array or a CPU torch tensor");
+  const py::array arr = py::reinterpret_borrow<py::array>(a);
+  if (!(arr.dtype().kind() == 'f' && arr.itemsize() == 8))
+    throw py::value_error(name + " must have dtype float64");
+  if (arr.ndim() != 2 || arr.shape(0) != s.M + 1 || arr.shape(1) != s.N + 1)
+    throw py::value_error(name + " must have shape (M+1, N+1) = (" + std::to_string(s.M + 1) + ", " +
+                          std::to_string(s.N + 1) + ")");
+  f.arr = py::array_t<double, py::array::c_style>::ensure(arr);
+  if (!f.arr) throw py::value_error(name + ": cannot be read as a C-contiguous float64 array");
+  const double* d = f.arr.data();
+  for (py::ssize_t k = 0; k < f.arr.size(); ++k)
+    if (!std::isfinite(d[k])) throw py::value_error(name + " holds non-finite values");
+  f.ptr = d;
+  return f;
 }
 
 py::dict sd_dict(const Subdomain& s) {
@@ -273,17 +307,25 @@ PYBIND11_MODULE(_pmx, m) {
   });
 
   // ---- CPU oracle ----
-  m.def("cpu_solve", [](const ProblemSpec& s, int threads, bool keep) {
+  // rhs / w0: optional (M+1) x (N+1) float64 arrays, see pmx/cpu_pcg.hpp
+  m.def("cpu_solve", [](const ProblemSpec& s, int threads, bool keep, py::object rhs, py::object w0) {
+          s.validate();
+          const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
           SolveResult r;
-          { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep); }
+          { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep, f.ptr, w.ptr); }
           return result_dict(r, s, keep);
-        }, py::arg("spec"), py::arg("threads") = 1, py::arg("keep_solution") = true);
-  m.def("cpu_solve_decomposed", [](const ProblemSpec& s, int nranks, Split split, int threads, bool keep) {
+        }, py::arg("spec"), py::arg("threads") = 1, py::arg("keep_solution") = true,
+        py::arg("rhs") = py::none(), py::arg("w0") = py::none());
+  m.def("cpu_solve_decomposed", [](const ProblemSpec& s, int nranks, Split split, int threads, bool keep,
+                                   py::object rhs, py::object w0) {
+          s.validate();
+          const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
           SolveResult r;
-          { py::gil_scoped_release nogil; r = cpu_solve_decomposed(s, nranks, split, threads, keep); }
+          { py::gil_scoped_release nogil; r = cpu_solve_decomposed(s, nranks, split, threads, keep, f.ptr, w.ptr); }
           return result_dict(r, s, keep);
         }, py::arg("spec"), py::arg("nranks"), py::arg("split") = Split::kReference,
-        py::arg("threads") = 1, py::arg("keep_solution") = true);
+        py::arg("threads") = 1, py::arg("keep_solution") = true, py::arg("rhs") = py::none(),
+        py::arg("w0") = py::none());
   m.def("cpu_assemble", [](const ProblemSpec& s) {
     std::vector<double> a, b, B;
     cpu_assemble(s, a, b, B);
@@ -562,14 +604,29 @@ PYBIND11_MODULE(_pmx, m) {
              { py::gil_scoped_release g; v = s.partials(i); }
              return to_numpy(v, {py::ssize_t(v.size() / 5), 5});
            }, py::arg("i") = 0, "per-tile partial sums of the last sweep (tests of the reduction hand-off)")
-      .def("init", [](Session& s) { py::gil_scoped_release g; s.init(); })
+      .def("init", [](Session& s, py::object rhs, py::object w0) {
+             const ProblemSpec& sp = s.solver(0).spec();
+             const FieldArg f = field_arg(rhs, sp, "rhs"), w = field_arg(w0, sp, "w0");
+             py::gil_scoped_release g;
+             s.init(f.ptr, w.ptr);
+           }, py::arg("rhs") = py::none(), py::arg("w0") = py::none(),
+           "start a solve; rhs / w0: optional (M+1) x (N+1) float64 right-hand side (masked to the ellipse) and "
+           "initial iterate, consumed by this init and not retained")
+      .def("residual_norm", [](Session& s, py::object rhs) {
+             const FieldArg f = field_arg(rhs, s.solver(0).spec(), "rhs");
+             py::gil_scoped_release g;
+             return s.residual_norm(f.ptr);
+           }, py::arg("rhs") = py::none(),
+           "sqrt(h1 h2 sum (B - A w)^2) of the current w, computed on the device (world == 1)")
       .def("step", [](Session& s, int64_t n) { py::gil_scoped_release g; s.step(n); })
       .def("synchronize", [](Session& s) { py::gil_scoped_release g; s.synchronize(); })
-      .def("solve", [](Session& s, int poll) {
+      .def("solve", [](Session& s, int poll, py::object rhs, py::object w0) {
+             const ProblemSpec& sp = s.solver(0).spec();
+             const FieldArg f = field_arg(rhs, sp, "rhs"), w = field_arg(w0, sp, "w0");
              RunStats r;
-             { py::gil_scoped_release g; r = s.solve(poll); }
+             { py::gil_scoped_release g; r = s.solve(f.ptr, w.ptr, poll); }
              return stats_dict(r);
-           }, py::arg("poll_batches") = 1)
+           }, py::arg("poll_batches") = 1, py::arg("rhs") = py::none(), py::arg("w0") = py::none())
       .def("solve_checkpointed", [](Session& s, const std::string& path, int64_t every, bool resume,
                                     int poll) {
              RunStats r;

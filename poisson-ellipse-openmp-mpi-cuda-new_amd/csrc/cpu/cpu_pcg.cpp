@@ -56,7 +56,8 @@ void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<d
     for (int j = 1; j <= N - 1; ++j) B[size_t(i) * pB + j] = geo::rhs(t, spec, i, j);
 }
 
-SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution) {
+SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, const double* rhs,
+                      const double* w0) {
   spec.validate();
   const GridInfo g(spec);
   const geo::FaceTables t(spec, g);
@@ -75,7 +76,11 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution) 
       b[size_t(i) * P + j] = geo::coef_b(t, g, i, j);
     }
   for (int i = 1; i <= M - 1; ++i)
-    for (int j = 1; j <= N - 1; ++j) r[size_t(i) * P + j] = geo::rhs(t, spec, i, j);
+    for (int j = 1; j <= N - 1; ++j) {
+      const size_t g = size_t(i) * (N + 1) + j;
+      r[size_t(i) * P + j] = !rhs ? geo::rhs(t, spec, i, j) : geo::rhs_mask(t, spec, i, j) ? rhs[g] : 0.0;
+      if (w0) w[size_t(i) * P + j] = w0[g];
+    }
 
   Timer timer;
   auto dot = [&](const std::vector<double>& u, const std::vector<double>& v) {
@@ -105,6 +110,12 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution) 
       }
   };
 
+  if (w0) {  // r^0 = B - A w0
+    p = w;
+    mat_A();
+    for (int i = 1; i <= M - 1; ++i)
+      for (int j = 1; j <= N - 1; ++j) r[size_t(i) * P + j] -= Ap[size_t(i) * P + j];
+  }
   mat_D();
   p = z;
   double zr_old = dot(z, r);
@@ -154,7 +165,8 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution) 
 // CpuSubdomain (stage2-mpi/poisson_mpi_decomp.cpp:124-232 semantics)
 // ---------------------------------------------------------------------------
 
-CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads)
+CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads, const double* rhs,
+                           const double* w0)
     : spec_(spec), g_(spec), sd_(sd), threads_(threads < 1 ? 1 : threads) {
   const geo::FaceTables t(spec, g_);
   const int nx = sd.nx, ny = sd.ny, P = ny + 2;
@@ -170,13 +182,37 @@ CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int thr
       b_[size_t(li) * P + lj] = geo::coef_b(t, g_, gi, gj);
     }
   for (int li = 1; li <= nx; ++li)
-    for (int lj = 1; lj <= ny; ++lj)
-      B_[size_t(li) * P + lj] = geo::rhs(t, spec, sd.gi0() + li, sd.gj0() + lj);
+    for (int lj = 1; lj <= ny; ++lj) {
+      const int gi = sd.gi0() + li, gj = sd.gj0() + lj;
+      B_[size_t(li) * P + lj] = !rhs ? geo::rhs(t, spec, gi, gj)
+                                : geo::rhs_mask(t, spec, gi, gj) ? rhs[size_t(gi) * (spec.N + 1) + gj] : 0.0;
+    }
+  if (w0) {  // with the ring, straight from the global array (boundary nodes count as 0)
+    w0_.assign(n, 0.0);
+    for (int li = 0; li <= nx + 1; ++li)
+      for (int lj = 0; lj <= ny + 1; ++lj) {
+        const int gi = sd.gi0() + li, gj = sd.gj0() + lj;
+        if (gi >= 1 && gi <= spec.M - 1 && gj >= 1 && gj <= spec.N - 1)
+          w0_[size_t(li) * P + lj] = w0[size_t(gi) * (spec.N + 1) + gj];
+      }
+  }
 }
 
 double CpuSubdomain::init() {
   r_ = B_;
   std::fill(w_.begin(), w_.end(), 0.0);
+  if (!w0_.empty()) {  // r^0 = B - A w0 (matvec_dot's arithmetic on p = w0 with its ring)
+    p_ = w0_;
+    (void)matvec_dot();
+    const int nx = sd_.nx, ny = sd_.ny, P = ny + 2;
+    for (int li = 1; li <= nx; ++li)
+      for (int lj = 1; lj <= ny; ++lj) {
+        const size_t c = size_t(li) * P + lj;
+        r_[c] -= Ap_[c];
+        w_[c] = w0_[c];
+      }
+    std::fill(p_.begin(), p_.end(), 0.0);
+  }
   const double zr = precond_dot();
   p_ = z_;
   return zr;
@@ -317,13 +353,14 @@ SolveResult cpu_pcg_loop(const ProblemSpec& spec, std::vector<CpuSubdomain*>& lo
 }
 
 SolveResult cpu_solve_decomposed(const ProblemSpec& spec, int nranks, Split split,
-                                 int threads_per_rank, bool keep_solution) {
+                                 int threads_per_rank, bool keep_solution, const double* rhs,
+                                 const double* w0) {
   spec.validate();
   const ProcGrid pg = make_process_grid(nranks, spec.M, spec.N, split);
   std::vector<CpuSubdomain> subs;
   subs.reserve(nranks);
   for (int r = 0; r < nranks; ++r)
-    subs.emplace_back(spec, decompose_2d(spec.M, spec.N, pg, r), threads_per_rank);
+    subs.emplace_back(spec, decompose_2d(spec.M, spec.N, pg, r), threads_per_rank, rhs, w0);
   std::vector<CpuSubdomain*> local;
   for (auto& s : subs) local.push_back(&s);
 

@@ -627,12 +627,7 @@ void GpuSubdomainSolver::progress(long long out[3]) const {
     out[q] = progress_host_ ? __atomic_load_n(progress_host_ + q, __ATOMIC_RELAXED) : -1;
 }
 
-ErrorStats GpuSubdomainSolver::error_norms(hipStream_t s) const {
-  HIP_CHECK(hipSetDevice(opt_.device));
-  const PcgState st = read_state(s);
-  // pending w steps, exactly as download_w applies them
-  const void* pp[2] = {nullptr, nullptr};
-  double a[2] = {0.0, 0.0};
+int GpuSubdomainSolver::pending_w(const PcgState& st, const void* pp[2], double a[2]) const {
   int npend = 0;
   if (pcg1_ && st.w_pend_n > 0 && st.w_pend > 0) {
     npend = st.w_pend_n;
@@ -646,6 +641,89 @@ ErrorStats GpuSubdomainSolver::error_norms(hipStream_t s) const {
     pp[0] = field_base((st.w_pend & 1) ? 3 : 2);
     a[0] = st.alpha[st.w_pend & 1];
   }
+  return npend;
+}
+
+namespace {
+// rows x cols doubles with row stride ld -> the storage type, dense
+std::vector<char> round_to_storage(const double* v, size_t rows, size_t cols, size_t ld, size_t elem) {
+  std::vector<char> out(rows * cols * elem);
+  for (size_t i = 0; i < rows; ++i) {
+    const double* src = v + i * ld;
+    if (elem == 8) {
+      std::memcpy(out.data() + i * cols * 8, src, cols * 8);
+    } else {
+      float* o = reinterpret_cast<float*>(out.data()) + i * cols;
+      for (size_t k = 0; k < cols; ++k) o[k] = static_cast<float>(src[k]);
+    }
+  }
+  return out;
+}
+}  // namespace
+
+void GpuSubdomainSolver::set_init_data(const double* f, const double* w0, int64_t ld_f, int64_t ld_w0) {
+  const size_t nx = size_t(sd_.nx), ny = size_t(sd_.ny);
+  stage_f_ = f ? round_to_storage(f, nx, ny, ld_f ? size_t(ld_f) : ny, elem_) : std::vector<char>();
+  stage_w_ = w0 ? round_to_storage(w0, nx + 2, ny + 2, ld_w0 ? size_t(ld_w0) : ny + 2, elem_) : std::vector<char>();
+}
+
+template <typename T>
+static void residual_launch(const DevGeom& G, const DevTables& Tb, const void* w, const void* f, int64_t ny,
+                            const void* const pp[2], const double a[2], int npend, double* part,
+                            const TileCfg& tc, hipStream_t s) {
+  InitData<T> X;
+  // f is dense nx x ny: element (i, j), i, j >= 1, at f[(i - 1) * ny + (j - 1)]
+  X.f = f ? static_cast<const T*>(f) - (ny + 1) : nullptr;
+  X.fpitch = ny;
+  X.pa = static_cast<const T*>(pp[0]);
+  X.pb = static_cast<const T*>(pp[1]);
+  X.ca = a[0];
+  X.cb = a[1];
+  X.npend = npend;
+  launch_init_data<T>(G, Tb, const_cast<T*>(static_cast<const T*>(w)), nullptr, HaloBufs<T>{}, part, tc, X, true, s);
+}
+
+double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_t ld_f) const {
+  HIP_CHECK(hipSetDevice(opt_.device));
+  const PcgState st = read_state(s);
+  const void* pp[2] = {nullptr, nullptr};
+  double a[2] = {0.0, 0.0};
+  const int npend = pending_w(st, pp, a);
+  // temporary device memory for the call: one partial pair per init tile, and f in the storage type
+  const size_t nt = size_t(init_tiles_.ntiles());
+  const std::vector<char> hf =
+      f ? round_to_storage(f, size_t(sd_.nx), size_t(sd_.ny), ld_f ? size_t(ld_f) : size_t(sd_.ny), elem_) : std::vector<char>();
+  char* tmp = nullptr;
+  HIP_CHECK(hipMalloc(&tmp, 2 * nt * sizeof(double) + hf.size()));
+  double* part = reinterpret_cast<double*>(tmp);
+  char* df = f ? tmp + 2 * nt * sizeof(double) : nullptr;
+  std::vector<double> h(2 * nt);
+  try {
+    if (f) HIP_CHECK(hipMemcpyAsync(df, hf.data(), hf.size(), hipMemcpyHostToDevice, s));
+    if (elem_ == 8)
+      residual_launch<double>(geom_, tables_, field_base(0), df, sd_.ny, pp, a, npend, part, init_tiles_, s);
+    else
+      residual_launch<float>(geom_, tables_, field_base(0), df, sd_.ny, pp, a, npend, part, init_tiles_, s);
+    HIP_CHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(tmp);
+    throw;
+  }
+  HIP_CHECK(hipFree(tmp));
+  double sum = 0.0;
+  for (size_t t = 0; t < nt; ++t) sum += h[2 * t + 1];  // tile order: deterministic
+  return sum;
+}
+
+ErrorStats GpuSubdomainSolver::error_norms(hipStream_t s) const {
+  HIP_CHECK(hipSetDevice(opt_.device));
+  const PcgState st = read_state(s);
+  // pending w steps, exactly as download_w applies them
+  const void* pp[2] = {nullptr, nullptr};
+  double a[2] = {0.0, 0.0};
+  const int npend = pending_w(st, pp, a);
   constexpr int kMaxBlocks = 1024;
   double* d_out = nullptr;
   HIP_CHECK(hipMalloc(&d_out, 3 * kMaxBlocks * sizeof(double)));
@@ -811,8 +889,36 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
   // k_init packs r^0 into the two-sweep send buffers; pcg1 packs its own radius-2 halo
   DevGeom G = geom_;
   if (pcg1_) G.nb = 0;
-  launch_init<T>(G, tables_, w, r, halo<T>(), partials_, init_tiles_, s);
-  after_launch(s);
+  if (has_init_data()) {
+    // user data (set_init_data), after the memsets above: f into r's owned nodes, w0 into w's owned
+    // nodes and ring; r <- B - A w0; then w's ring is zero again, as every later kernel and the
+    // checkpoints expect of w's ghosts
+    const size_t P = size_t(geom_.pitch) * sizeof(T), nx = size_t(sd_.nx), ny = size_t(sd_.ny);
+    InitData<T> X;
+    X.fpitch = geom_.pitch;
+    X.has_f = !stage_f_.empty();
+    X.has_w = !stage_w_.empty();
+    if (X.has_f)
+      HIP_CHECK(hipMemcpy2DAsync(r + geom_.pitch + 1, P, stage_f_.data(), ny * sizeof(T), ny * sizeof(T), nx,
+                                 hipMemcpyHostToDevice, s));
+    if (X.has_w)
+      HIP_CHECK(hipMemcpy2DAsync(w, P, stage_w_.data(), (ny + 2) * sizeof(T), (ny + 2) * sizeof(T), nx + 2,
+                                 hipMemcpyHostToDevice, s));
+    launch_init_data<T>(G, tables_, w, r, halo<T>(), partials_, init_tiles_, X, false, s);
+    after_launch(s);
+    if (X.has_w) {
+      HIP_CHECK(hipMemsetAsync(w, 0, (ny + 2) * sizeof(T), s));
+      HIP_CHECK(hipMemsetAsync(w + (nx + 1) * size_t(geom_.pitch), 0, (ny + 2) * sizeof(T), s));
+      HIP_CHECK(hipMemset2DAsync(w + geom_.pitch, P, 0, sizeof(T), nx, s));
+      HIP_CHECK(hipMemset2DAsync(w + geom_.pitch + ny + 1, P, 0, sizeof(T), nx, s));
+    }
+    HIP_CHECK(hipStreamSynchronize(s));  // the staged host copies are read until here
+    std::vector<char>().swap(stage_f_);
+    std::vector<char>().swap(stage_w_);
+  } else {
+    launch_init<T>(G, tables_, w, r, halo<T>(), partials_, init_tiles_, s);
+    after_launch(s);
+  }
   launch_reduce(partials_, init_tiles_.ntiles(), 2, 0.0, g_.h1h2, state_->red_b, state_, 0, reduce_ws_, s);
   after_launch(s);
   if (ca_) {  // set 0: z^0 = D^-1 r^0 (in r's buffer), p^0 = z^0; block counter 0

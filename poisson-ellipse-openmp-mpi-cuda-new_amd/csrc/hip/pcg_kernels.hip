@@ -42,11 +42,27 @@ TileCfg make_tiles(const DevGeom& G, int block, int rows) {
 
 // ---------------------------------------------------------------------------
 // r = B, w = 0, partial (z0, r0) with z0 = D^-1 r0, pack r edges
+//
+// MODE kInitData: the initial residual from user data.  r holds f on the owned nodes (X.has_f;
+// else the constant G.F) and w holds w0 on the owned nodes and a 1-cell ring (X.has_w; else
+// w0 = 0): r <- T(B - A w0) with B = f inside D and 0 outside, A in the reference's operation
+// order (apply_a<true>) on the same on-the-fly faces, w0 = 0 on the global boundary.  w is only
+// read; every thread reads and writes its own cell of r.  Same tiles, march and (z0, r0) partial
+// as the plain mode.
+// MODE kInitMeasure: nothing is stored; the partial is the sum of (B - A w)^2 over the tile, w with
+// its pending steps applied as k_error_norms applies them, f from X.f (nullptr: G.F).
+// Each thread keeps the w rows i-1, i, i+1 of its column in registers and takes the j-1 / j+1
+// neighbours by plain loads.
 // ---------------------------------------------------------------------------
-template <typename T, int BLOCK>
+__device__ __forceinline__ double resid(double B, double Aw) {
+  PMX_NO_CONTRACT
+  return B - Aw;
+}
+
+template <typename T, int BLOCK, int MODE>
 __global__ void __launch_bounds__(BLOCK)
 k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T> H,
-       double* __restrict__ partials, int TI, int tiles_j) {
+       double* __restrict__ partials, int TI, int tiles_j, InitData<T> X) {
   __shared__ double lds[2 * BLOCK / kWave];
   const Tile t = tile_of(blockIdx.x, tiles_j, TI, BLOCK, G);
   const int j = t.j0 + threadIdx.x;
@@ -55,25 +71,67 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
     const int gj = G.gj0 + j;
     const ColConst cc = load_col(Tb, gj);
     const double yj = Tb.y[gj];
+    const int64_t P = G.pitch;
+    // w (MODE != kInitPlain): pending steps applied in measure mode, rounded to the storage type
+    auto wl = [&](int64_t c) {
+      double v = double(w[c]);
+      if constexpr (MODE == kInitMeasure) {
+        if (X.npend > 0) v = __builtin_fma(X.ca, double(X.pa[c]), v);
+        if (X.npend > 1) v = __builtin_fma(X.cb, double(X.pb[c]), v);
+        if (X.npend > 0 && sizeof(T) == 4) v = double(static_cast<float>(v));
+      }
+      return v;
+    };
+    const bool has_w = MODE == kInitMeasure || (MODE == kInitData && X.has_w);
+    const bool djm = gj - 1 <= 0, djp = gj + 1 >= G.N;  // Dirichlet neighbours count as 0
+    double wm = 0.0, wc = 0.0;
+    if (MODE != kInitPlain && has_w) {
+      wm = G.gi0 + t.i0 - 1 <= 0 ? 0.0 : wl(int64_t(t.i0 - 1) * P + j);
+      wc = wl(int64_t(t.i0) * P + j);
+    }
     for (int i = t.i0; i <= t.iend; ++i) {
       const int gi = G.gi0 + i;
       const RowConst rc = load_row(Tb, gi);
       const double a0 = face_a(cc, rc.rv0, G), a1 = face_a(cc, rc.rv1, G);
       const double b0 = face_b(rc, cc.rh0, G), b1 = face_b(rc, cc.rh1, G);
+      const int64_t c = int64_t(i) * P + j;
       // B_ij = F inside D (stage0/Withoutopenmp1.cpp:60)
-      const double B = geo::inside(Tb.x[gi], yj, G.ax, G.by, G.ref_ellipse != 0) ? G.F : 0.0;
-      const T Bs = static_cast<T>(B);
+      const bool in = geo::inside(Tb.x[gi], yj, G.ax, G.by, G.ref_ellipse != 0);
+      T Bs;
+      if constexpr (MODE == kInitPlain) {
+        Bs = static_cast<T>(in ? G.F : 0.0);
+      } else {
+        const T* fsrc = MODE == kInitData ? (X.has_f ? r : nullptr) : X.f;
+        Bs = fsrc ? (in ? fsrc[int64_t(i) * X.fpitch + j] : T(0)) : static_cast<T>(in ? G.F : 0.0);
+      }
       const double Bq = static_cast<double>(Bs);
-      const double D = diag<true>(a0, a1, b0, b1, G);
-      const double z = (D != 0.0) ? Bq / D : 0.0;
-      acc += z * Bq;
-      const int64_t c = int64_t(i) * G.pitch + j;
-      r[c] = Bs;
-      w[c] = T(0);
-      if (i == 1 && (G.nb & kNbXlo)) H.send[0][j - 1] = Bs;
-      if (i == G.nx && (G.nb & kNbXhi)) H.send[1][j - 1] = Bs;
-      if (j == 1 && (G.nb & kNbYlo)) H.send[2][i - 1] = Bs;
-      if (j == G.ny && (G.nb & kNbYhi)) H.send[3][i - 1] = Bs;
+      if constexpr (MODE == kInitMeasure) {
+        const double wp = gi + 1 >= G.M ? 0.0 : wl(c + P);
+        const double wjm = djm ? 0.0 : wl(c - 1), wjp = djp ? 0.0 : wl(c + 1);
+        const double e = resid(Bq, apply_a<true>(wc, wm, wp, wjm, wjp, a0, a1, b0, b1, G));
+        acc = __builtin_fma(e, e, acc);
+        wm = wc;
+        wc = wp;
+      } else {
+        T rs = Bs;
+        if (MODE == kInitData && has_w) {
+          const double wp = gi + 1 >= G.M ? 0.0 : wl(c + P);
+          const double wjm = djm ? 0.0 : wl(c - 1), wjp = djp ? 0.0 : wl(c + 1);
+          rs = static_cast<T>(resid(Bq, apply_a<true>(wc, wm, wp, wjm, wjp, a0, a1, b0, b1, G)));
+          wm = wc;
+          wc = wp;
+        }
+        const double rq = static_cast<double>(rs);
+        const double D = diag<true>(a0, a1, b0, b1, G);
+        const double z = (D != 0.0) ? rq / D : 0.0;
+        acc += z * rq;
+        r[c] = rs;
+        if constexpr (MODE == kInitPlain) w[c] = T(0);
+        if (i == 1 && (G.nb & kNbXlo)) H.send[0][j - 1] = rs;
+        if (i == G.nx && (G.nb & kNbXhi)) H.send[1][j - 1] = rs;
+        if (j == 1 && (G.nb & kNbYlo)) H.send[2][i - 1] = rs;
+        if (j == G.ny && (G.nb & kNbYhi)) H.send[3][i - 1] = rs;
+      }
     }
   }
   block_sum2<BLOCK>(acc, unused, lds);
@@ -198,8 +256,21 @@ template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
                  double* partials, const TileCfg& tc, hipStream_t s) {
   PMX_BLOCK_DISPATCH(tc.block,
-      hipLaunchKernelGGL((k_init<T, B>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
-                         partials, tc.rows, tc.tiles_j));
+      hipLaunchKernelGGL((k_init<T, B, kInitPlain>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
+                         partials, tc.rows, tc.tiles_j, InitData<T>{}));
+  HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
+                      const TileCfg& tc, const InitData<T>& X, bool measure, hipStream_t s) {
+  PMX_CHECK(tc.block == 256, "the data init runs the init tiling (256 columns per tile)");
+  if (measure)
+    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+                       partials, tc.rows, tc.tiles_j, X);
+  else
+    hipLaunchKernelGGL((k_init<T, 256, kInitData>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+                       partials, tc.rows, tc.tiles_j, X);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -234,6 +305,9 @@ void launch_local_allreduce(double* const* bufs, int nranks, int nq, hipStream_t
 #define PMX_INST(T)                                                                              \
   template void launch_init<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>, double*,  \
                                const TileCfg&, hipStream_t);                                     \
+  template void launch_init_data<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>,       \
+                                    double*, const TileCfg&, const InitData<T>&, bool,           \
+                                    hipStream_t);                                                 \
   template void launch_edge_r<T>(const DevGeom&, const DevTables&, const T*, const T*, const T*, \
                                  HaloBufs<T>, const PcgState*, bool, hipStream_t);
 PMX_INST(double)

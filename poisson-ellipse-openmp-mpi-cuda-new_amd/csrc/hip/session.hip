@@ -203,6 +203,43 @@ void Session::init() {
   for_drivers([](size_t, PcgDriver& d) { d.init(); });
 }
 
+void Session::stage_init_data(const double* rhs, const double* w0) {
+  if (!rhs && !w0) return;
+  PMX_CHECK(cfg_.comm == CommKind::kSelf || cfg_.comm == CommKind::kLocal,
+            "a right-hand side / initial guess needs a session that owns every subdomain (world 1 or the "
+            "local communicator); multi-process sessions are not supported");
+  // every subdomain reads its block straight out of the global arrays (row stride N + 1): f from its
+  // first owned node, w0 one node earlier in both directions, i.e. with its ring -- the neighbours'
+  // values, so nothing is exchanged for w0
+  const int64_t ld = cfg_.spec.N + 1;
+  for (auto& sp : solvers_) {
+    const Subdomain& sd = sp->sd();
+    const int64_t o = int64_t(sd.gi0()) * ld + sd.gj0();  // local (0, 0)
+    sp->set_init_data(rhs ? rhs + o + ld + 1 : nullptr, w0 ? w0 + o : nullptr, ld, ld);
+  }
+}
+
+void Session::init(const double* rhs, const double* w0) {
+  require_connected();
+  stage_init_data(rhs, w0);
+  init();
+}
+
+RunStats Session::solve(const double* rhs, const double* w0, int poll_batches) {
+  require_connected();
+  stage_init_data(rhs, w0);
+  return solve(poll_batches);
+}
+
+double Session::residual_norm(const double* rhs) {
+  PMX_CHECK(cfg_.world == 1, "residual_norm runs undecomposed sessions (world == 1): w has no ghost exchange");
+  synchronize();
+  GpuSubdomainSolver& g = *solvers_[0];
+  const int64_t ld = cfg_.spec.N + 1;  // the owned nodes start at global (1, 1)
+  const GridInfo gi(cfg_.spec);
+  return std::sqrt(gi.h1h2 * g.residual_sumsq(rhs ? rhs + ld + 1 : nullptr, stream_of(0), ld));
+}
+
 void Session::step(int64_t n) {
   for_drivers([n](size_t, PcgDriver& d) { d.enqueue_iterations(n); });
 }

@@ -29,7 +29,11 @@ struct SolveResult {
 };
 
 // Serial (threads<=1) or OpenMP PCG over the whole grid.
-SolveResult cpu_solve(const ProblemSpec& spec, int threads = 1, bool keep_solution = true);
+// rhs / w0: optional global (M+1) x (N+1) row-major arrays.  rhs replaces the constant F as
+// right-hand side under the ellipse mask (B = rhs inside D, 0 elsewhere; boundary nodes ignored),
+// w0 the zero initial iterate (its boundary nodes count as 0): r^0 = B - A w0 in mat_A's arithmetic.
+SolveResult cpu_solve(const ProblemSpec& spec, int threads = 1, bool keep_solution = true,
+                      const double* rhs = nullptr, const double* w0 = nullptr);
 
 // Assemble the reference's 2D arrays on the host (tests: kernel bit-equality).
 // a, b are (M+2) x (N+2) including ghost nodes; B is (M+1) x (N+1).
@@ -39,12 +43,14 @@ void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<d
 // One rank's block (local arrays (nx+2) x (ny+2), row-major, pitch ny+2).
 class CpuSubdomain {
  public:
-  CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads);
+  // rhs / w0: as cpu_solve (global arrays; this block, and for w0 its ring, are copied)
+  CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads, const double* rhs = nullptr,
+               const double* w0 = nullptr);
 
   const Subdomain& sd() const { return sd_; }
   int pitch() const { return sd_.ny + 2; }
 
-  double init();                         // r=B, z=D^-1 r, p=z, w=0 -> local (z,r)
+  double init();                         // r=B-A w0, z=D^-1 r, p=z, w=w0 (0) -> local (z,r)
   double matvec_dot();                   // Ap = A p (needs p halos) -> local (Ap,p)
   void update_wr(double alpha, double* diff_local);   // w+=ap, r-=aAp, local sum dw^2
   double precond_dot();                  // z = D^-1 r -> local (z,r)
@@ -66,13 +72,15 @@ class CpuSubdomain {
   Subdomain sd_;
   int threads_;
   std::vector<double> a_, b_, B_, w_, r_, z_, p_, Ap_;
+  std::vector<double> w0_;  // initial iterate with its ring (empty: zero)
 };
 
 // In-process multi-subdomain driver: P subdomains stepped in lock-step with a
 // deterministic rank-ordered reduction.  This is the "fake cluster" used to test
 // decomposition + halo logic without MPI (SURVEY §4.2 'distributed (fake)').
 SolveResult cpu_solve_decomposed(const ProblemSpec& spec, int nranks, Split split,
-                                 int threads_per_rank = 1, bool keep_solution = true);
+                                 int threads_per_rank = 1, bool keep_solution = true,
+                                 const double* rhs = nullptr, const double* w0 = nullptr);
 
 // Generic lock-step PCG over CpuSubdomains with pluggable collectives.  The MPI
 // app supplies MPI-backed callbacks; the in-process driver supplies local ones.

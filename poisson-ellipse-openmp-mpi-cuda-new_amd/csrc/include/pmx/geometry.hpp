@@ -142,8 +142,11 @@ inline double coef_a(const FaceTables& t, const GridInfo& g, int i, int j) {
 inline double coef_b(const FaceTables& t, const GridInfo& g, int i, int j) {
   return face_coef(clip_len(t.xlo[i], t.xhi[i], t.rh[j]), g.h1, g.eps, g.inv_eps);
 }
+inline bool rhs_mask(const FaceTables& t, const ProblemSpec& s, int i, int j) {
+  return inside(t.x[i], t.y[j], s.ax, s.by, s.reference_ellipse());
+}
 inline double rhs(const FaceTables& t, const ProblemSpec& s, int i, int j) {
-  return inside(t.x[i], t.y[j], s.ax, s.by, s.reference_ellipse()) ? s.F : 0.0;
+  return rhs_mask(t, s, i, j) ? s.F : 0.0;
 }
 
 }  // namespace geo

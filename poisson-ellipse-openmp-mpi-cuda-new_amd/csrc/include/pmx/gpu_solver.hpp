@@ -248,6 +248,20 @@ class GpuSubdomainSolver {
   // r=B, w=0, p=0, state reset, red_b <- (0, zr_0).  Single-pass: the driver then runs the ghost
   // exchange of r^0 (decomposed grids), sweep 0 (enqueue_phase_a) and the all-reduce of red_c.
   void enqueue_init(hipStream_t s);
+  // Data for the NEXT enqueue_init only: f (nx x ny, the owned nodes) replaces the constant F as
+  // right-hand side (the ellipse mask still applies), w0 ((nx+2) x (ny+2), owned nodes and a 1-cell
+  // ring holding the neighbours' values) the zero initial iterate: r^0 = B - A w0.  Either may be
+  // null.  The values are rounded to the storage type here and held on the host until that init
+  // has uploaded them (it then waits for its stream); a later plain init is the cold constant-F
+  // start again.  Nothing stays allocated.  ld_f / ld_w0: the arrays' row strides in elements
+  // (0: dense), so a caller can point into a larger array.  Ring values on the global boundary are
+  // ignored (Dirichlet).
+  void set_init_data(const double* f, const double* w0, int64_t ld_f = 0, int64_t ld_w0 = 0);
+  bool has_init_data() const { return !stage_f_.empty() || !stage_w_.empty(); }
+  // sum over the owned nodes of (B - A w)^2 for the current w (pending steps applied, as
+  // download_w), B from `f` (nx x ny, null: the constant F) under the ellipse mask; w's ghost
+  // ring counts as zero, so this is the residual of an undecomposed solver.  Synchronous.
+  double residual_sumsq(const double* f, hipStream_t s, int64_t ld_f = 0) const;
   void enqueue_phase_a(hipStream_t s);  // k_pcg_a + reduce -> red_a
   // the two halves of each phase, for per-step timing (PcgDriver::profile_phases)
   void enqueue_kernel_a(hipStream_t s);
@@ -446,6 +460,10 @@ class GpuSubdomainSolver {
   bool direct_rows_ = false;
   long long halo_target_ = 0;
   TileCfg init_tiles_{};
+  // set_init_data: f / w0 in the storage type, dense, until the next init uploads them
+  std::vector<char> stage_f_, stage_w_;
+  // pending w steps as download_w applies them: fields and factors, returns their number
+  int pending_w(const PcgState& st, const void* pp[2], double a[2]) const;
   CommLayout layout_{};
   size_t elem_ = 8, field_bytes_ = 0, field_off_ = 0;
   // Fields w, r, p0, p1 (and pcg1's r2) in ONE allocation, field f at fields_ + f * field_stride_;

@@ -86,6 +86,28 @@ template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
                  double* partials, const TileCfg& tc, hipStream_t s);
 
+// k_init with data (GpuSubdomainSolver::set_init_data / residual_norm), on launch_init's tiling.
+//   data init (measure = false): r holds f on the owned nodes (has_f; else the constant G.F), w holds
+//     w0 on the owned nodes and a 1-cell ring (has_w; else w0 = 0).  r <- T(B - A w0), B = f inside D
+//     and 0 outside; the (z0, r0) partials and pcg2's packed r edges as launch_init.  w is only read.
+//   measure: nothing is stored; partials[2 t + 1] = sum over tile t of (B - A w)^2, w with the
+//     npend pending steps w + ca pa (+ cb pb) applied as launch_error_norms applies them; B from f
+//     (element (i, j) at f[i * fpitch + j]; nullptr: G.F).  r and H are unused.
+enum InitMode : int { kInitPlain = 0, kInitData = 1, kInitMeasure = 2 };
+template <typename T>
+struct InitData {
+  const T* f = nullptr;
+  int64_t fpitch = 0;  // data init: the fields' pitch (f is read from r)
+  int has_f = 0, has_w = 0;
+  const T* pa = nullptr;
+  const T* pb = nullptr;
+  double ca = 0.0, cb = 0.0;
+  int npend = 0;
+};
+template <typename T>
+void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
+                      const TileCfg& tc, const InitData<T>& X, bool measure, hipStream_t s);
+
 template <typename T>
 void launch_pcg_a_wave(const DevGeom& G, const DevTables& Tb, const T* r, T* p0, T* p1,
                        HaloBufs<T> H, double* partials, PcgState* S, const TileCfg& tc, bool exact,

@@ -50,6 +50,17 @@ class Session {
   bool connected() const { return !drivers_.empty(); }
 
   void init();
+  // init from user data: `rhs` replaces the constant F as right-hand side (the solver applies the
+  // ellipse mask: B = rhs inside D, 0 elsewhere), `w0` the zero initial iterate (r^0 = B - A w0; its
+  // boundary nodes count as 0).  Global (M+1) x (N+1) row-major arrays, either may be null.  Every
+  // subdomain gets its block (w0 with its ring, so no exchange of w0 is needed); the data is consumed
+  // by this init and not retained: a later init() is the constant-F cold start.  Sessions that own every
+  // subdomain (world 1, local communicator) only.
+  void init(const double* rhs, const double* w0);
+  RunStats solve(const double* rhs, const double* w0, int poll_batches = 1);
+  // sqrt(h1 h2 sum (B - A w)^2) over the interior for the w gather_local_w() returns, computed on the
+  // device; B from `rhs` ((M+1) x (N+1), null: the constant F) under the ellipse mask.  world == 1.
+  double residual_norm(const double* rhs = nullptr);
   void step(int64_t n);
   void synchronize();
   RunStats solve(int poll_batches = 1);
@@ -103,6 +114,7 @@ class Session {
   // to its rank's device) in threaded mode; the first exception is rethrown after all joined
   void for_drivers(const std::function<void(size_t, PcgDriver&)>& f);
   RunStats solve_impl(int poll_batches, bool do_init, int64_t every, const std::string& save_path);
+  void stage_init_data(const double* rhs, const double* w0);  // GpuSubdomainSolver::set_init_data on every solver
 
   SessionConfig cfg_;
   ProcGrid pg_;

@@ -103,11 +103,33 @@ class PoissonEllipse:
         return {"sum_e2": float((e * e).sum()), "max_error": float(np.abs(e).max(initial=0.0)),
                 "max_w": float(local.max(initial=-np.inf))}
 
-    def error_norms(self, w: np.ndarray) -> dict:
-        """L2 (h-weighted) and max error of a (M+1)x(N+1) solution vs the analytic one, in D."""
+    def field(self, a, name: str = "field") -> Optional[np.ndarray]:
+        """A user field (rhs, w0, exact) as a C-contiguous float64 (M+1)x(N+1) array, or None.
+
+        Accepts NumPy arrays and CPU torch tensors; ValueError for any other type, dtype or shape, for a
+        device tensor and for non-finite values (the native entry points apply the same rules)."""
+        if a is None:
+            return None
+        if hasattr(a, "numpy") and hasattr(a, "device"):  # a torch tensor
+            if a.device.type != "cpu":
+                raise ValueError(f"{name}: device tensors are not supported, pass a NumPy array or a CPU tensor")
+            a = a.detach().numpy()
+        if not isinstance(a, np.ndarray):
+            raise ValueError(f"{name} must be a NumPy array or a CPU torch tensor")
+        if a.dtype != np.float64:
+            raise ValueError(f"{name} must have dtype float64, got {a.dtype}")
+        if a.shape != (self.M + 1, self.N + 1):
+            raise ValueError(f"{name} must have shape (M+1, N+1) = {(self.M + 1, self.N + 1)}, got {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"{name} holds non-finite values")
+        return np.ascontiguousarray(a)
+
+    def error_norms(self, w: np.ndarray, exact: Optional[np.ndarray] = None) -> dict:
+        """L2 (h-weighted) and max error of a (M+1)x(N+1) solution in D, vs the analytic solution of the
+        constant-F problem or, for another right-hand side, vs `exact` ((M+1)x(N+1) values of its solution)."""
         x, y = self.coords()
         X, Y = np.meshgrid(x, y, indexing="ij")
-        u = self.exact_solution(X, Y)
+        u = self.exact_solution(X, Y) if exact is None else self.field(exact, "exact")
         m = self.inside_mask()
         e = np.where(m, w - u, 0.0)
         return {

@@ -46,6 +46,9 @@ class Result:
 
 
 def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
+    """rhs / w0 (every backend): optional (M+1)x(N+1) float64 arrays -- a right-hand side f(x_i, y_j) in
+    place of the constant F (the solver applies the ellipse mask: values outside D and on the box
+    boundary are ignored) and an initial iterate in place of w = 0."""
     if backend in ("cpu", "serial"):
         return solve_cpu(problem, threads=1, **kw)
     if backend in ("omp", "openmp"):
@@ -57,21 +60,22 @@ def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
     if backend == "torch":
         from .torch_pcg import TorchPCG
 
-        return TorchPCG(problem, **kw).solve()
+        rhs, w0 = kw.pop("rhs", None), kw.pop("w0", None)
+        return TorchPCG(problem, **kw).solve(rhs=rhs, w0=w0)
     raise ValueError(f"unknown backend {backend!r}")
 
 
-def solve_cpu(problem: PoissonEllipse, threads: int = 1, keep_solution: bool = True) -> Result:
-    r = _native().cpu_solve(problem.to_native(), int(threads), bool(keep_solution))
+def solve_cpu(problem: PoissonEllipse, threads: int = 1, keep_solution: bool = True, rhs=None, w0=None) -> Result:
+    r = _native().cpu_solve(problem.to_native(), int(threads), bool(keep_solution), rhs=rhs, w0=w0)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
                   backend="cpu" if threads <= 1 else f"omp{threads}")
 
 
 def solve_cpu_decomposed(problem: PoissonEllipse, ranks: int = 4, split: str = "reference",
-                         threads: int = 1, keep_solution: bool = True) -> Result:
+                         threads: int = 1, keep_solution: bool = True, rhs=None, w0=None) -> Result:
     n = _native()
     r = n.cpu_solve_decomposed(problem.to_native(), int(ranks), getattr(n.Split, split), int(threads),
-                               bool(keep_solution))
+                               bool(keep_solution), rhs=rhs, w0=w0)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
                   backend="cpu-decomposed", ranks=ranks)
 
@@ -115,10 +119,12 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
 
 
 def solve_hip(problem: PoissonEllipse, ranks: int = 1, keep_solution: bool = True, poll_batches: int = 1,
-              **session_kw) -> Result:
+              rhs=None, w0=None, **session_kw) -> Result:
+    """rhs / w0: see solve(); the session uploads them for this solve and retains nothing
+    (Session.init(rhs=..., w0=...))."""
     t0 = time.perf_counter()
     s = make_session(problem, ranks=ranks, **session_kw)
-    st = s.solve(poll_batches)
+    st = s.solve(poll_batches, rhs=rhs, w0=w0)
     w = s.gather_local_w() if keep_solution else None
     r = Result(st["iters"], st["status"], st["diff"], st["solve_seconds"], w, backend="hip", ranks=ranks,
                init_seconds=st["init_seconds"],

@@ -42,11 +42,37 @@ class TorchPCG:
         return float(self.comm.allreduce_(t).item())
 
     # ---- stepwise interface (same contract as the native Session: init / step / state) ----
-    def init(self):
+    def _local(self, g):
+        """This rank's block of a global (M+1)x(N+1) array with its ghost ring, global boundary zeroed."""
+        sd = self.sd
+        t = torch.as_tensor(g[sd["i_start"] - 1:sd["i_end"] + 2, sd["j_start"] - 1:sd["j_end"] + 2].copy())
+        if sd["i_start"] == 1:
+            t[0, :] = 0
+        if sd["i_end"] == self.p.M - 1:
+            t[-1, :] = 0
+        if sd["j_start"] == 1:
+            t[:, 0] = 0
+        if sd["j_end"] == self.p.N - 1:
+            t[:, -1] = 0
+        return t.to(device=self.device, dtype=self.dtype)
+
+    def init(self, rhs=None, w0=None):
+        """rhs / w0: optional global (M+1)x(N+1) float64 arrays (NumPy or CPU tensors): B = rhs inside D
+        (0 elsewhere) in place of the constant F, and the initial iterate, r^0 = B - A w0."""
         P = self.p
         h1, h2 = P.h1, P.h2
+        rhs, w0 = P.field(rhs, "rhs"), P.field(w0, "w0")
         self.w = torch.zeros(self.B.shape, dtype=self.dtype, device=self.device)
         self.r = self.B.clone()
+        if rhs is not None:
+            inside = R.inside(P, self.sd, self.device)
+            self.r = torch.where(inside, self._local(rhs), torch.zeros_like(self.B))
+            for edge in (self.r[0, :], self.r[-1, :], self.r[:, 0], self.r[:, -1]):
+                edge.zero_()
+        if w0 is not None:
+            wl = self._local(w0)  # the ring comes from the global array: no exchange
+            self.r[1:-1, 1:-1] -= R.apply_A(wl, self.a, self.b, h1, h2)
+            self.w[1:-1, 1:-1] = wl[1:-1, 1:-1]
         self.pv = torch.zeros_like(self.w)
         z = R.precond(self.r, self.a, self.b, h1, h2)
         self.pv[1:-1, 1:-1] = z
@@ -105,10 +131,10 @@ class TorchPCG:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
-    def solve(self, keep_solution: bool = True) -> Result:
+    def solve(self, keep_solution: bool = True, rhs=None, w0=None) -> Result:
         P = self.p
         t0 = time.perf_counter()
-        self.init()
+        self.init(rhs=rhs, w0=w0)
         while not self.done:
             self.step(64)
         seconds = time.perf_counter() - t0

@@ -48,6 +48,16 @@ def local_index(sd):
     return gi, gj
 
 
+def inside(problem, sd, device="cpu"):
+    """The ellipse mask of the RHS over the local array incl. ghosts, shape (nx+2, ny+2)."""
+    T = face_tables(problem, device)
+    gi, gj = local_index(sd)
+    x, y = T["x"][gi.to(device)][:, None], T["y"][gj.to(device)][None, :]
+    if problem.is_reference_ellipse():
+        return x * x + 4.0 * y * y < 1.0
+    return (x / problem.ax) ** 2 + (y / problem.by) ** 2 < 1.0
+
+
 def assemble(problem, sd, device="cpu", dtype=torch.float64):
     """a, b over the local array incl. ghosts, B (RHS) on the interior.  Shapes (nx+2, ny+2)."""
     T = face_tables(problem, device)
@@ -57,12 +67,8 @@ def assemble(problem, sd, device="cpu", dtype=torch.float64):
     xlo, xhi, rh = T["xlo"][gi][:, None], T["xhi"][gi][:, None], T["rh"][gj][None, :]
     a = _face_coef(_clip_len(ylo, yhi, rv), problem.h2, problem.eps)
     b = _face_coef(_clip_len(xlo, xhi, rh), problem.h1, problem.eps)
-    x, y = T["x"][gi][:, None], T["y"][gj][None, :]
-    if problem.is_reference_ellipse():
-        inside = x * x + 4.0 * y * y < 1.0
-    else:
-        inside = (x / problem.ax) ** 2 + (y / problem.by) ** 2 < 1.0
-    B = torch.where(inside, torch.full_like(x * y, problem.F), torch.zeros_like(x * y))
+    mask = inside(problem, sd, device)
+    B = torch.where(mask, torch.full_like(a, problem.F), torch.zeros_like(a))
     B[0, :] = 0
     B[-1, :] = 0
     B[:, 0] = 0
