@@ -20,6 +20,7 @@ Fixed studies (STUDIES) and parametrised ones (`<study> -- <arguments>`):
     ca_ab     -- bench/probe/ca_env_ab.py arguments: same-process A/B of s-step knobs
     algos     -- MxN:algo:dtype: bench.py per grid x algorithm x storage
     counters  -- kernel trace + SQ / EA counter passes of one bench.py configuration
+    device_io -- bench/probe/device_io.py arguments: host-array vs device-tensor init and gather times
     cmds      -- ad-hoc steps 'tag:seconds:command'
 Studies that back kept profiles name themselves in the profile's README; bench/RETIRED.md maps
 the round-1/2 one-off gpu_*.sh scripts onto these.
@@ -262,6 +263,12 @@ def _counters(argv):
     return steps + pmc_study("counters", {"c": env}, a.args, ("sq1", "sq2", "ea_rd", "ea_wr"))
 
 
+def _device_io(argv):
+    """NumPy against device-tensor init / gather and the torch copy_ yardstick, one process: the arguments
+    (--M --N --reps --dtypes --ranks --algo --iters) go to bench/probe/device_io.py"""
+    return [("device_io", 400, "python -u bench/probe/device_io.py " + " ".join(shlex.quote(a) for a in argv))]
+
+
 def _cmds(argv):
     """ad-hoc steps, one per argument 'tag:seconds:command' (python commands of this repo)"""
     steps = []
@@ -272,7 +279,7 @@ def _cmds(argv):
 
 
 PARAMETRISED = {"cmds": _cmds, "ab": _ab, "pmc": _pmc, "timeline": _timeline, "validate": _validate, "share": _share, "cli": _cli,
-                "loopback": _loopback, "ca_ab": _ca_ab, "algos": _algos, "counters": _counters}
+                "loopback": _loopback, "ca_ab": _ca_ab, "algos": _algos, "counters": _counters, "device_io": _device_io}
 
 
 def script(name: str, steps) -> str:

@@ -64,6 +64,77 @@ FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::strin
   return f;
 }
 
+// The stream a device array was produced on / will be consumed on.  A torch tensor: the current torch
+// stream of its device (asked through Python, no torch C++).  Any other exporter: the interface's
+// optional `stream` entry (1: the legacy default stream, 2: the per-thread default one), else the
+// legacy default stream.
+hipStream_t array_stream(const py::object& obj, const py::dict& cai) {
+  const std::string mod = py::str(py::type::of(obj).attr("__module__"));
+  if (mod == "torch" || mod.rfind("torch.", 0) == 0) {
+    const py::object st = py::module_::import("torch").attr("cuda").attr("current_stream")(obj.attr("device"));
+    return as_stream(st.attr("cuda_stream").cast<uintptr_t>());
+  }
+  if (cai.contains("stream") && !cai["stream"].is_none()) {
+    const uintptr_t v = cai["stream"].cast<uintptr_t>();
+    return v == 1 ? nullptr : v == 2 ? hipStreamPerThread : as_stream(v);
+  }
+  return nullptr;
+}
+
+// A device array through `__cuda_array_interface__` (torch ROCm tensors export it) as a UserField:
+// typestr <f8, shape (M+1, N+1), unit column stride, row stride >= N+1 elements (a column-sliced view
+// of a wider array passes), memory of device `device`; `writable`: not read-only.  ValueError otherwise.
+UserField device_field(const py::object& obj, const ProblemSpec& s, int device, const std::string& name,
+                       bool writable = false) {
+  const py::dict cai = obj.attr("__cuda_array_interface__").cast<py::dict>();
+  if (cai["typestr"].cast<std::string>() != "<f8")
+    throw py::value_error(name + ": a device array must have dtype float64");
+  const py::tuple shape = cai["shape"].cast<py::tuple>();
+  if (shape.size() != 2 || shape[0].cast<int64_t>() != s.M + 1 || shape[1].cast<int64_t>() != s.N + 1)
+    throw py::value_error(name + " must have shape (M+1, N+1) = (" + std::to_string(s.M + 1) + ", " +
+                          std::to_string(s.N + 1) + ")");
+  UserField f;
+  f.ld = s.N + 1;
+  if (cai.contains("strides") && !cai["strides"].is_none()) {
+    const py::tuple st = cai["strides"].cast<py::tuple>();
+    const int64_t s0 = st.size() == 2 ? st[0].cast<int64_t>() : 0, s1 = st.size() == 2 ? st[1].cast<int64_t>() : 0;
+    if (s1 != 8 || s0 % 8 != 0 || s0 / 8 < s.N + 1)
+      throw py::value_error(name + ": a device array needs unit column stride and a row stride >= N+1 elements");
+    f.ld = s0 / 8;
+  }
+  const py::tuple data = cai["data"].cast<py::tuple>();
+  if (writable && data[1].cast<bool>()) throw py::value_error(name + " is read-only");
+  f.ptr = reinterpret_cast<const double*>(data[0].cast<uintptr_t>());
+  hipPointerAttribute_t attr;
+  if (!f.ptr || hipPointerGetAttributes(&attr, f.ptr) != hipSuccess || attr.type != hipMemoryTypeDevice) {
+    (void)hipGetLastError();
+    throw py::value_error(name + ": not a device allocation");
+  }
+  if (attr.device != device)
+    throw py::value_error(name + " lives on device " + std::to_string(attr.device) + ", the session on device " +
+                          std::to_string(device));
+  f.on_device = true;
+  f.stream = array_stream(obj, cai);
+  return f;
+}
+
+// rhs / w0 of a Session method: a device array (device_field) or what field_arg takes
+struct SessionField {
+  FieldArg host;
+  UserField f;
+};
+SessionField session_field(const py::object& obj, Session& s, const std::string& name) {
+  SessionField r;
+  const ProblemSpec& sp = s.solver(0).spec();
+  if (!obj.is_none() && py::hasattr(obj, "__cuda_array_interface__")) {
+    r.f = device_field(obj, sp, s.solver(0).device(), name);
+  } else {
+    r.host = field_arg(obj, sp, name);
+    r.f = UserField(r.host.ptr);
+  }
+  return r;
+}
+
 py::dict sd_dict(const Subdomain& s) {
   py::dict d;
   d["M"] = s.M; d["N"] = s.N; d["Px"] = s.grid.Px; d["Py"] = s.grid.Py;
@@ -605,28 +676,57 @@ PYBIND11_MODULE(_pmx, m) {
              return to_numpy(v, {py::ssize_t(v.size() / 5), 5});
            }, py::arg("i") = 0, "per-tile partial sums of the last sweep (tests of the reduction hand-off)")
       .def("init", [](Session& s, py::object rhs, py::object w0) {
-             const ProblemSpec& sp = s.solver(0).spec();
-             const FieldArg f = field_arg(rhs, sp, "rhs"), w = field_arg(w0, sp, "w0");
+             const SessionField f = session_field(rhs, s, "rhs"), w = session_field(w0, s, "w0");
              py::gil_scoped_release g;
-             s.init(f.ptr, w.ptr);
+             s.init(f.f, w.f);
            }, py::arg("rhs") = py::none(), py::arg("w0") = py::none(),
            "start a solve; rhs / w0: optional (M+1) x (N+1) float64 right-hand side (masked to the ellipse) and "
-           "initial iterate, consumed by this init and not retained")
+           "initial iterate, consumed by this init and not retained.  Each is a NumPy array, a CPU tensor or a "
+           "device array (__cuda_array_interface__, e.g. a torch tensor on the session's device; unit column "
+           "stride, row stride >= N+1).  A device array is read in place by a kernel, after the work already "
+           "enqueued on its producer's stream (a torch tensor: the current torch stream of its device) -- the "
+           "caller adds no synchronisation -- and has been consumed when the call returns")
       .def("residual_norm", [](Session& s, py::object rhs) {
-             const FieldArg f = field_arg(rhs, s.solver(0).spec(), "rhs");
+             const SessionField f = session_field(rhs, s, "rhs");
              py::gil_scoped_release g;
-             return s.residual_norm(f.ptr);
+             return s.residual_norm(f.f);
            }, py::arg("rhs") = py::none(),
-           "sqrt(h1 h2 sum (B - A w)^2) of the current w, computed on the device (world == 1)")
+           "sqrt(h1 h2 sum (B - A w)^2) of the current w, computed on the device (world == 1); rhs as in init "
+           "(a device array is ordered after its producer's stream and read in place)")
+      .def("gather_w_device", [](Session& s, py::object out) {
+             const UserField o = device_field(out, s.solver(0).spec(), s.solver(0).device(), "out", true);
+             py::gil_scoped_release g;
+             s.gather_w_device(const_cast<double*>(o.ptr), o.ld, o.stream);
+           }, py::arg("out"),
+           "gather_local_w() into a float64 device array of shape (M+1, N+1) (unit column stride, row stride "
+           ">= N+1; elements past column N of a row are not touched).  Ordered after the work already enqueued "
+           "on the array's stream (a torch tensor: the current torch stream) and visible to work enqueued there "
+           "afterwards; the caller adds no synchronisation")
+      .def("w_tensor", [](py::object self, py::object out) {
+             Session& s = self.cast<Session&>();
+             if (out.is_none()) {
+               const ProblemSpec& sp = s.solver(0).spec();
+               const py::module_ torch = py::module_::import("torch");
+               out = torch.attr("empty")(py::make_tuple(sp.M + 1, sp.N + 1), py::arg("dtype") = torch.attr("float64"),
+                                         py::arg("device") = torch.attr("device")("cuda", s.solver(0).device()));
+             } else if (!py::hasattr(out, "__cuda_array_interface__")) {
+               throw py::value_error("out must be a float64 device tensor of shape (M+1, N+1)");
+             }
+             self.attr("gather_w_device")(out);
+             return out;
+           }, py::arg("out") = py::none(),
+           "the solution gather_local_w() returns, bitwise, as a torch.float64 tensor on the session's device, "
+           "written by a kernel without passing through the host; out: a tensor to fill (see gather_w_device) "
+           "instead of a new one.  Usable at once on the current torch stream")
       .def("step", [](Session& s, int64_t n) { py::gil_scoped_release g; s.step(n); })
       .def("synchronize", [](Session& s) { py::gil_scoped_release g; s.synchronize(); })
       .def("solve", [](Session& s, int poll, py::object rhs, py::object w0) {
-             const ProblemSpec& sp = s.solver(0).spec();
-             const FieldArg f = field_arg(rhs, sp, "rhs"), w = field_arg(w0, sp, "w0");
+             const SessionField f = session_field(rhs, s, "rhs"), w = session_field(w0, s, "w0");
              RunStats r;
-             { py::gil_scoped_release g; r = s.solve(f.ptr, w.ptr, poll); }
+             { py::gil_scoped_release g; r = s.solve(f.f, w.f, poll); }
              return stats_dict(r);
-           }, py::arg("poll_batches") = 1, py::arg("rhs") = py::none(), py::arg("w0") = py::none())
+           }, py::arg("poll_batches") = 1, py::arg("rhs") = py::none(), py::arg("w0") = py::none(),
+           "init(rhs, w0) and iterate to the stop decision; rhs / w0 as in init, device arrays included")
       .def("solve_checkpointed", [](Session& s, const std::string& path, int64_t every, bool resume,
                                     int poll) {
              RunStats r;

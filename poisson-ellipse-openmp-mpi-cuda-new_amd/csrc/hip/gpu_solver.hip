@@ -665,16 +665,32 @@ void GpuSubdomainSolver::set_init_data(const double* f, const double* w0, int64_
   const size_t nx = size_t(sd_.nx), ny = size_t(sd_.ny);
   stage_f_ = f ? round_to_storage(f, nx, ny, ld_f ? size_t(ld_f) : ny, elem_) : std::vector<char>();
   stage_w_ = w0 ? round_to_storage(w0, nx + 2, ny + 2, ld_w0 ? size_t(ld_w0) : ny + 2, elem_) : std::vector<char>();
+  dev_f_ = dev_w_ = nullptr;  // each call replaces the data of the next init
+}
+
+void GpuSubdomainSolver::set_init_data_device(const double* f, const double* w0, int64_t ld_f, int64_t ld_w0) {
+  PMX_CHECK(!f || ld_f >= sd_.ny, "row stride of the device right-hand side below the block's width");
+  PMX_CHECK(!w0 || ld_w0 >= sd_.ny + 2, "row stride of the device initial guess below the block's width");
+  if (f) {
+    std::vector<char>().swap(stage_f_);
+    dev_f_ = f;
+    dev_ld_f_ = ld_f;
+  }
+  if (w0) {
+    std::vector<char>().swap(stage_w_);
+    dev_w_ = w0;
+    dev_ld_w_ = ld_w0;
+  }
 }
 
 template <typename T>
-static void residual_launch(const DevGeom& G, const DevTables& Tb, const void* w, const void* f, int64_t ny,
+static void residual_launch(const DevGeom& G, const DevTables& Tb, const void* w, const void* f, int64_t fpitch,
                             const void* const pp[2], const double a[2], int npend, double* part,
                             const TileCfg& tc, hipStream_t s) {
   InitData<T> X;
-  // f is dense nx x ny: element (i, j), i, j >= 1, at f[(i - 1) * ny + (j - 1)]
-  X.f = f ? static_cast<const T*>(f) - (ny + 1) : nullptr;
-  X.fpitch = ny;
+  // f is nx x ny with row stride fpitch: element (i, j), i, j >= 1, at f[(i - 1) * fpitch + (j - 1)]
+  X.f = f ? static_cast<const T*>(f) - (fpitch + 1) : nullptr;
+  X.fpitch = fpitch;
   X.pa = static_cast<const T*>(pp[0]);
   X.pb = static_cast<const T*>(pp[1]);
   X.ca = a[0];
@@ -683,27 +699,35 @@ static void residual_launch(const DevGeom& G, const DevTables& Tb, const void* w
   launch_init_data<T>(G, Tb, const_cast<T*>(static_cast<const T*>(w)), nullptr, HaloBufs<T>{}, part, tc, X, true, s);
 }
 
-double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_t ld_f) const {
+double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_t ld_f, bool f_on_device) const {
   HIP_CHECK(hipSetDevice(opt_.device));
+  PMX_CHECK(!(f && f_on_device) || ld_f >= sd_.ny, "a device right-hand side needs its row stride");
   const PcgState st = read_state(s);
   const void* pp[2] = {nullptr, nullptr};
   double a[2] = {0.0, 0.0};
   const int npend = pending_w(st, pp, a);
   // temporary device memory for the call: one partial pair per init tile, and f in the storage type
+  // (a device f in fp64 storage is read where it lies)
   const size_t nt = size_t(init_tiles_.ntiles());
+  const bool host_f = f && !f_on_device, in_place = f && f_on_device && elem_ == 8;
   const std::vector<char> hf =
-      f ? round_to_storage(f, size_t(sd_.nx), size_t(sd_.ny), ld_f ? size_t(ld_f) : size_t(sd_.ny), elem_) : std::vector<char>();
+      host_f ? round_to_storage(f, size_t(sd_.nx), size_t(sd_.ny), ld_f ? size_t(ld_f) : size_t(sd_.ny), elem_)
+             : std::vector<char>();
+  const size_t fbytes = f && !in_place ? size_t(sd_.nx) * size_t(sd_.ny) * elem_ : 0;
   char* tmp = nullptr;
-  HIP_CHECK(hipMalloc(&tmp, 2 * nt * sizeof(double) + hf.size()));
+  HIP_CHECK(hipMalloc(&tmp, 2 * nt * sizeof(double) + fbytes));
   double* part = reinterpret_cast<double*>(tmp);
-  char* df = f ? tmp + 2 * nt * sizeof(double) : nullptr;
+  const void* df = !f ? nullptr : in_place ? static_cast<const void*>(f) : tmp + 2 * nt * sizeof(double);
+  const int64_t fpitch = in_place ? ld_f : sd_.ny;
   std::vector<double> h(2 * nt);
   try {
-    if (f) HIP_CHECK(hipMemcpyAsync(df, hf.data(), hf.size(), hipMemcpyHostToDevice, s));
+    if (host_f) HIP_CHECK(hipMemcpyAsync(tmp + 2 * nt * sizeof(double), hf.data(), hf.size(), hipMemcpyHostToDevice, s));
+    if (f && f_on_device && !in_place)
+      launch_scatter<float>(f, ld_f, reinterpret_cast<float*>(tmp + 2 * nt * sizeof(double)), sd_.ny, sd_.nx, sd_.ny, s);
     if (elem_ == 8)
-      residual_launch<double>(geom_, tables_, field_base(0), df, sd_.ny, pp, a, npend, part, init_tiles_, s);
+      residual_launch<double>(geom_, tables_, field_base(0), df, fpitch, pp, a, npend, part, init_tiles_, s);
     else
-      residual_launch<float>(geom_, tables_, field_base(0), df, sd_.ny, pp, a, npend, part, init_tiles_, s);
+      residual_launch<float>(geom_, tables_, field_base(0), df, fpitch, pp, a, npend, part, init_tiles_, s);
     HIP_CHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   } catch (...) {
@@ -896,12 +920,18 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     const size_t P = size_t(geom_.pitch) * sizeof(T), nx = size_t(sd_.nx), ny = size_t(sd_.ny);
     InitData<T> X;
     X.fpitch = geom_.pitch;
-    X.has_f = !stage_f_.empty();
-    X.has_w = !stage_w_.empty();
-    if (X.has_f)
+    X.has_f = !stage_f_.empty() || dev_f_;
+    X.has_w = !stage_w_.empty() || dev_w_;
+    // the same cells from either source: a staged host copy, or the caller's device block through the
+    // scatter kernel (set_init_data_device)
+    if (dev_f_)
+      launch_scatter<T>(dev_f_, dev_ld_f_, r + geom_.pitch + 1, geom_.pitch, sd_.nx, sd_.ny, s);
+    else if (X.has_f)
       HIP_CHECK(hipMemcpy2DAsync(r + geom_.pitch + 1, P, stage_f_.data(), ny * sizeof(T), ny * sizeof(T), nx,
                                  hipMemcpyHostToDevice, s));
-    if (X.has_w)
+    if (dev_w_)
+      launch_scatter<T>(dev_w_, dev_ld_w_, w, geom_.pitch, sd_.nx + 2, sd_.ny + 2, s);
+    else if (X.has_w)
       HIP_CHECK(hipMemcpy2DAsync(w, P, stage_w_.data(), (ny + 2) * sizeof(T), (ny + 2) * sizeof(T), nx + 2,
                                  hipMemcpyHostToDevice, s));
     launch_init_data<T>(G, tables_, w, r, halo<T>(), partials_, init_tiles_, X, false, s);
@@ -912,9 +942,10 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
       HIP_CHECK(hipMemset2DAsync(w + geom_.pitch, P, 0, sizeof(T), nx, s));
       HIP_CHECK(hipMemset2DAsync(w + geom_.pitch + ny + 1, P, 0, sizeof(T), nx, s));
     }
-    HIP_CHECK(hipStreamSynchronize(s));  // the staged host copies are read until here
+    HIP_CHECK(hipStreamSynchronize(s));  // the staged host copies / the caller's device blocks are read until here
     std::vector<char>().swap(stage_f_);
     std::vector<char>().swap(stage_w_);
+    dev_f_ = dev_w_ = nullptr;
   } else {
     launch_init<T>(G, tables_, w, r, halo<T>(), partials_, init_tiles_, s);
     after_launch(s);
@@ -1369,6 +1400,27 @@ std::vector<double> GpuSubdomainSolver::download_w(hipStream_t s) const {
       out[size_t(li - 1) * sd_.ny + (lj - 1)] = v;
     }
   return out;
+}
+
+void GpuSubdomainSolver::gather_w_device(double* out, int64_t ld, hipStream_t s) const {
+  HIP_CHECK(hipSetDevice(opt_.device));
+  PMX_CHECK(out && ld >= spec_.N + 1, "gather_w_device needs an (M+1) x (N+1) array with row stride >= N+1");
+  const PcgState st = read_state(s);
+  const void* pp[2] = {nullptr, nullptr};
+  double a[2] = {0.0, 0.0};
+  const int npend = pending_w(st, pp, a);
+  // the owned nodes, widened by the global boundary row / column where the block touches it
+  const int li0 = sd_.gi0() == 0 ? 0 : 1, li1 = sd_.gi0() + sd_.nx + 1 == spec_.M ? sd_.nx + 1 : sd_.nx;
+  const int lj0 = sd_.gj0() == 0 ? 0 : 1, lj1 = sd_.gj0() + sd_.ny + 1 == spec_.N ? sd_.ny + 1 : sd_.ny;
+  if (elem_ == 8)
+    launch_gather<double>(static_cast<const double*>(field_base(0)), static_cast<const double*>(pp[0]), a[0],
+                          static_cast<const double*>(pp[1]), a[1], npend, geom_.pitch, out, ld, li0, lj0,
+                          li1 - li0 + 1, lj1 - lj0 + 1, sd_.gi0(), sd_.gj0(), spec_.M, spec_.N, s);
+  else
+    launch_gather<float>(static_cast<const float*>(field_base(0)), static_cast<const float*>(pp[0]), a[0],
+                         static_cast<const float*>(pp[1]), a[1], npend, geom_.pitch, out, ld, li0, lj0,
+                         li1 - li0 + 1, lj1 - lj0 + 1, sd_.gi0(), sd_.gj0(), spec_.M, spec_.N, s);
+  after_launch(s);
 }
 
 }  // namespace pmx

@@ -1,0 +1,121 @@
+// Device-resident user data: a global row-major fp64 array (row stride ld elements, unit column
+// stride) <-> the per-subdomain pitched fields, without a staging buffer on either side.
+//
+//   k_scatter  a block of the global array -> a field (or any pitched T buffer), rounded to the storage
+//              type as the host path's round_to_storage: copied for double, static_cast for float
+//   k_finite   raises a flag on any non-finite value of the whole array
+//   k_gather   w of one subdomain, pending steps applied as GpuSubdomainSolver::download_w applies them,
+//              -> its block of the global array; global boundary nodes are written as zero
+//
+// Plain streaming kernels.  Lanes run along a row, a workgroup covers kIoCols columns of kIoRows rows
+// and issues its row loads before the first store.  ld = N + 1 is odd in general, so a row of the
+// global array starts at any 8-B boundary and the fields' rows are entered at column 1: every access
+// is one element per lane (8 B, 4 B for fp32 fields), coalesced, and nothing wider is attempted.
+// Stores to the fields are non-temporal like the sweeps' (the next reader is another kernel).
+#include <cstdint>
+
+#include "pmx/common.hpp"
+#include "pmx/kernels.hpp"
+
+namespace pmx {
+
+namespace {
+
+constexpr int kIoCols = 256;  // threads per workgroup, one column each
+constexpr int kIoRows = 8;    // rows per workgroup
+
+dim3 io_grid(int rows, int cols) {
+  PMX_CHECK(rows > 0 && cols > 0, "empty block");
+  const int64_t gy = (int64_t(rows) + kIoRows - 1) / kIoRows;
+  PMX_CHECK(gy <= 65535, "too many rows for one launch: " << rows);
+  return dim3(unsigned((cols + kIoCols - 1) / kIoCols), unsigned(gy));
+}
+
+}  // namespace
+
+template <typename T>
+__global__ void __launch_bounds__(kIoCols)
+k_scatter(const double* __restrict__ src, int64_t ld, T* __restrict__ dst, int64_t pitch, int rows, int cols) {
+  const int j = blockIdx.x * kIoCols + threadIdx.x;
+  const int i0 = blockIdx.y * kIoRows;
+  if (j >= cols) return;
+  double v[kIoRows] = {};
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u)
+    if (i0 + u < rows) v[u] = src[int64_t(i0 + u) * ld + j];
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u)
+    if (i0 + u < rows) __builtin_nontemporal_store(static_cast<T>(v[u]), dst + int64_t(i0 + u) * pitch + j);
+}
+
+__global__ void __launch_bounds__(kIoCols)
+k_finite(const double* __restrict__ src, int64_t ld, int rows, int cols, int* flag) {
+  const int j = blockIdx.x * kIoCols + threadIdx.x;
+  const int i0 = blockIdx.y * kIoRows;
+  if (j >= cols) return;
+  constexpr unsigned long long kExp = 0x7ff0000000000000ull;  // all ones: inf or NaN
+  bool bad = false;
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u)
+    if (i0 + u < rows)
+      bad |= (static_cast<unsigned long long>(__double_as_longlong(src[int64_t(i0 + u) * ld + j])) & kExp) == kExp;
+  if (bad) *flag = 1;  // every writer stores the same value
+}
+
+// local nodes (li0 .. li0 + rows - 1) x (lj0 .. lj0 + cols - 1) of a subdomain whose local (0, 0) is
+// global (gi0, gj0); w, pa, pb point to local (0, 0)
+template <typename T>
+__global__ void __launch_bounds__(kIoCols)
+k_gather(const T* __restrict__ w, const T* __restrict__ pa, double ca, const T* __restrict__ pb, double cb,
+         int npend, int64_t pitch, double* __restrict__ out, int64_t ld, int li0, int lj0, int rows, int cols,
+         int gi0, int gj0, int M, int N) {
+  const int c = blockIdx.x * kIoCols + threadIdx.x;
+  const int r0 = blockIdx.y * kIoRows;
+  if (c >= cols) return;
+  const int lj = lj0 + c, gj = gj0 + lj;
+  double v[kIoRows];
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u) {
+    const int li = li0 + r0 + u, gi = gi0 + li;
+    v[u] = 0.0;
+    if (r0 + u < rows && gi > 0 && gi < M && gj > 0 && gj < N) {
+      const int64_t k = int64_t(li) * pitch + lj;
+      double x = double(w[k]);
+      if (npend > 0) x = __builtin_fma(ca, double(pa[k]), x);
+      if (npend > 1) x = __builtin_fma(cb, double(pb[k]), x);
+      if (npend > 0 && sizeof(T) == 4) x = double(static_cast<float>(x));
+      v[u] = x;
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u)
+    if (r0 + u < rows) out[int64_t(gi0 + li0 + r0 + u) * ld + gj] = v[u];
+}
+
+template <typename T>
+void launch_scatter(const double* src, int64_t ld, T* dst, int64_t pitch, int rows, int cols, hipStream_t s) {
+  hipLaunchKernelGGL((k_scatter<T>), io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, dst, pitch, rows, cols);
+  HIP_CHECK(hipGetLastError());
+}
+template void launch_scatter<double>(const double*, int64_t, double*, int64_t, int, int, hipStream_t);
+template void launch_scatter<float>(const double*, int64_t, float*, int64_t, int, int, hipStream_t);
+
+void launch_finite_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s) {
+  hipLaunchKernelGGL(k_finite, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);
+  HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void launch_gather(const T* w, const T* pa, double ca, const T* pb, double cb, int npend, int64_t pitch,
+                   double* out, int64_t ld, int li0, int lj0, int rows, int cols, int gi0, int gj0, int M, int N,
+                   hipStream_t s) {
+  hipLaunchKernelGGL((k_gather<T>), io_grid(rows, cols), dim3(kIoCols), 0, s, w, pa, ca, pb, cb, npend, pitch, out,
+                     ld, li0, lj0, rows, cols, gi0, gj0, M, N);
+  HIP_CHECK(hipGetLastError());
+}
+template void launch_gather<double>(const double*, const double*, double, const double*, double, int, int64_t,
+                                    double*, int64_t, int, int, int, int, int, int, int, int, hipStream_t);
+template void launch_gather<float>(const float*, const float*, double, const float*, double, int, int64_t, double*,
+                                   int64_t, int, int, int, int, int, int, int, int, hipStream_t);
+
+}  // namespace pmx

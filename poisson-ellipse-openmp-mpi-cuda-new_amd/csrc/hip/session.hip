@@ -203,41 +203,131 @@ void Session::init() {
   for_drivers([](size_t, PcgDriver& d) { d.init(); });
 }
 
-void Session::stage_init_data(const double* rhs, const double* w0) {
-  if (!rhs && !w0) return;
+void Session::require_owns_all(const char* what) const {
   PMX_CHECK(cfg_.comm == CommKind::kSelf || cfg_.comm == CommKind::kLocal,
-            "a right-hand side / initial guess needs a session that owns every subdomain (world 1 or the "
+            what << " needs a session that owns every subdomain (world 1 or the "
             "local communicator); multi-process sessions are not supported");
-  // every subdomain reads its block straight out of the global arrays (row stride N + 1): f from its
-  // first owned node, w0 one node earlier in both directions, i.e. with its ring -- the neighbours'
-  // values, so nothing is exchanged for w0
-  const int64_t ld = cfg_.spec.N + 1;
+}
+
+int Session::require_one_device() const {
+  const int dev = solvers_[0]->device();
+  for (auto& sp : solvers_)
+    PMX_CHECK(sp->device() == dev, "device fields need every subdomain of the session on one device");
+  return dev;
+}
+
+void Session::wait_for(hipStream_t producer) {
+  HIP_CHECK(hipSetDevice(require_one_device()));
+  hipEvent_t e = nullptr;
+  HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t err = hipEventRecord(e, producer);
+  for (size_t i = 0; i < solvers_.size() && err == hipSuccess; ++i) err = hipStreamWaitEvent(stream_of(int(i)), e, 0);
+  (void)hipEventDestroy(e);  // released once the waits enqueued above have passed it
+  HIP_CHECK(err);
+}
+
+void Session::check_finite(const UserField& rhs, const UserField& w0) {
+  const UserField* f[2] = {&rhs, &w0};
+  const char* name[2] = {"rhs", "w0"};
+  if (!(rhs && rhs.on_device) && !(w0 && w0.on_device)) return;
+  HIP_CHECK(hipSetDevice(require_one_device()));
+  const hipStream_t s = stream_of(0);
+  const int rows = cfg_.spec.M + 1, cols = cfg_.spec.N + 1;
+  int* flag = nullptr;  // one per field, for the call only
+  int h[2] = {0, 0};
+  HIP_CHECK(hipMalloc(&flag, sizeof(h)));
+  try {
+    HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(h), s));
+    for (int q = 0; q < 2; ++q)
+      if (*f[q] && f[q]->on_device)
+        launch_finite_check(f[q]->ptr, f[q]->ld ? f[q]->ld : cols, rows, cols, flag + q, s);
+    HIP_CHECK(hipMemcpyAsync(h, flag, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(flag);
+    throw;
+  }
+  HIP_CHECK(hipFree(flag));
+  for (int q = 0; q < 2; ++q)
+    if (h[q]) throw std::invalid_argument(std::string(name[q]) + " holds non-finite values");
+}
+
+void Session::stage_init_data(const UserField& rhs, const UserField& w0) {
+  if (!rhs && !w0) return;
+  require_owns_all("a right-hand side / initial guess");
+  // device fields: ordered after their producers' work, and checked before the session is touched
+  for (const UserField* f : {&rhs, &w0}) {
+    if (!*f || !f->on_device) continue;
+    PMX_CHECK(f->ld == 0 || f->ld >= cfg_.spec.N + 1, "row stride of a device field below N + 1");
+    if (f == &w0 && rhs && rhs.on_device && rhs.stream == w0.stream) continue;  // one wait serves both
+    wait_for(f->stream);
+  }
+  check_finite(rhs, w0);
+  // every subdomain reads its block straight out of the global arrays (row stride N + 1 unless the
+  // field says otherwise): f from its first owned node, w0 one node earlier in both directions, i.e.
+  // with its ring -- the neighbours' values, so nothing is exchanged for w0
+  const int64_t ldf = rhs.ld ? rhs.ld : cfg_.spec.N + 1, ldw = w0.ld ? w0.ld : cfg_.spec.N + 1;
   for (auto& sp : solvers_) {
     const Subdomain& sd = sp->sd();
-    const int64_t o = int64_t(sd.gi0()) * ld + sd.gj0();  // local (0, 0)
-    sp->set_init_data(rhs ? rhs + o + ld + 1 : nullptr, w0 ? w0 + o : nullptr, ld, ld);
+    // local (0, 0) of w0, the first owned node of rhs
+    const double* f = rhs ? rhs.ptr + (int64_t(sd.gi0()) + 1) * ldf + sd.gj0() + 1 : nullptr;
+    const double* w = w0 ? w0.ptr + int64_t(sd.gi0()) * ldw + sd.gj0() : nullptr;
+    sp->set_init_data(rhs.on_device ? nullptr : f, w0.on_device ? nullptr : w, ldf, ldw);
+    sp->set_init_data_device(rhs.on_device ? f : nullptr, w0.on_device ? w : nullptr, ldf, ldw);
   }
 }
 
-void Session::init(const double* rhs, const double* w0) {
+void Session::init(const UserField& rhs, const UserField& w0) {
   require_connected();
   stage_init_data(rhs, w0);
   init();
 }
 
-RunStats Session::solve(const double* rhs, const double* w0, int poll_batches) {
+RunStats Session::solve(const UserField& rhs, const UserField& w0, int poll_batches) {
   require_connected();
   stage_init_data(rhs, w0);
   return solve(poll_batches);
 }
 
-double Session::residual_norm(const double* rhs) {
+void Session::init(const double* rhs, const double* w0) { init(UserField(rhs), UserField(w0)); }
+
+RunStats Session::solve(const double* rhs, const double* w0, int poll_batches) {
+  return solve(UserField(rhs), UserField(w0), poll_batches);
+}
+
+double Session::residual_norm(const UserField& rhs) {
   PMX_CHECK(cfg_.world == 1, "residual_norm runs undecomposed sessions (world == 1): w has no ghost exchange");
   synchronize();
+  if (rhs && rhs.on_device) {
+    PMX_CHECK(rhs.ld == 0 || rhs.ld >= cfg_.spec.N + 1, "row stride of a device field below N + 1");
+    wait_for(rhs.stream);
+    check_finite(rhs, UserField());
+  }
   GpuSubdomainSolver& g = *solvers_[0];
-  const int64_t ld = cfg_.spec.N + 1;  // the owned nodes start at global (1, 1)
+  const int64_t ld = rhs.ld ? rhs.ld : cfg_.spec.N + 1;  // the owned nodes start at global (1, 1)
   const GridInfo gi(cfg_.spec);
-  return std::sqrt(gi.h1h2 * g.residual_sumsq(rhs ? rhs + ld + 1 : nullptr, stream_of(0), ld));
+  return std::sqrt(gi.h1h2 * g.residual_sumsq(rhs ? rhs.ptr + ld + 1 : nullptr, stream_of(0), ld, rhs.on_device));
+}
+
+double Session::residual_norm(const double* rhs) { return residual_norm(UserField(rhs)); }
+
+void Session::gather_w_device(double* out, int64_t ld, hipStream_t consumer) {
+  require_connected();
+  require_owns_all("a device solution");
+  PMX_CHECK(out && ld >= cfg_.spec.N + 1, "gather_w_device needs an (M+1) x (N+1) array with row stride >= N+1");
+  synchronize();
+  wait_for(consumer);  // earlier work on the consumer's stream may still use `out`
+  for (size_t i = 0; i < solvers_.size(); ++i) solvers_[i]->gather_w_device(out, ld, stream_of(int(i)));
+  hipEvent_t e = nullptr;
+  HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t err = hipSuccess;
+  for (size_t i = 0; i < solvers_.size() && err == hipSuccess; ++i) {
+    err = hipEventRecord(e, stream_of(int(i)));
+    if (err == hipSuccess) err = hipStreamWaitEvent(consumer, e, 0);
+  }
+  (void)hipEventDestroy(e);
+  HIP_CHECK(err);
 }
 
 void Session::step(int64_t n) {

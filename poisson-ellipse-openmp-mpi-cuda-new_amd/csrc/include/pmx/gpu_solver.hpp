@@ -257,11 +257,20 @@ class GpuSubdomainSolver {
   // (0: dense), so a caller can point into a larger array.  Ring values on the global boundary are
   // ignored (Dirichlet).
   void set_init_data(const double* f, const double* w0, int64_t ld_f = 0, int64_t ld_w0 = 0);
-  bool has_init_data() const { return !stage_f_.empty() || !stage_w_.empty(); }
+  // The device twin: the same blocks in fp64 device memory of this solver's device (row strides ld_f /
+  // ld_w0 elements).  Only the pointers are held; the next enqueue_init reads them on its stream with
+  // the scatter kernel (io_kernels.hip) -- rounded to the storage type on the way, no staging buffer --
+  // and waits for that stream, so the memory must stay valid and unchanged until that init returns.
+  // A null argument leaves what set_init_data staged for that array in place (one array may come from
+  // the host, the other from the device).
+  void set_init_data_device(const double* f, const double* w0, int64_t ld_f, int64_t ld_w0);
+  bool has_init_data() const { return !stage_f_.empty() || !stage_w_.empty() || dev_f_ || dev_w_; }
   // sum over the owned nodes of (B - A w)^2 for the current w (pending steps applied, as
   // download_w), B from `f` (nx x ny, null: the constant F) under the ellipse mask; w's ghost
   // ring counts as zero, so this is the residual of an undecomposed solver.  Synchronous.
-  double residual_sumsq(const double* f, hipStream_t s, int64_t ld_f = 0) const;
+  // f_on_device: f is device memory (ld_f required): fp64 storage reads it in place, fp32 storage
+  // rounds it into the call's temporary device buffer with the scatter kernel.
+  double residual_sumsq(const double* f, hipStream_t s, int64_t ld_f = 0, bool f_on_device = false) const;
   void enqueue_phase_a(hipStream_t s);  // k_pcg_a + reduce -> red_a
   // the two halves of each phase, for per-step timing (PcgDriver::profile_phases)
   void enqueue_kernel_a(hipStream_t s);
@@ -346,6 +355,11 @@ class GpuSubdomainSolver {
 
   // local interior of w (nx x ny, row-major) as fp64 on the host
   std::vector<double> download_w(hipStream_t s) const;
+  // The device twin: the same values, bitwise, written by the gather kernel (io_kernels.hip) on stream
+  // s into this subdomain's block of a global (M+1) x (N+1) fp64 device array, out[gi * ld + gj]; the
+  // global boundary nodes next to the block are written as zero, so the blocks of a decomposition tile
+  // the whole array.  Reads the scalars (synchronous), then enqueues; it does not wait for the kernel.
+  void gather_w_device(double* out, int64_t ld, hipStream_t s) const;
   // any local field (0 w, 1 r, 2 p0, 3 p1) including ghosts: (nx+2) x (ny+2)
   std::vector<double> download_field(int which, hipStream_t s) const;
 
@@ -462,6 +476,10 @@ class GpuSubdomainSolver {
   TileCfg init_tiles_{};
   // set_init_data: f / w0 in the storage type, dense, until the next init uploads them
   std::vector<char> stage_f_, stage_w_;
+  // set_init_data_device: the caller's device blocks and their row strides, until the next init
+  const double* dev_f_ = nullptr;
+  const double* dev_w_ = nullptr;
+  int64_t dev_ld_f_ = 0, dev_ld_w_ = 0;
   // pending w steps as download_w applies them: fields and factors, returns their number
   int pending_w(const PcgState& st, const void* pp[2], double a[2]) const;
   CommLayout layout_{};

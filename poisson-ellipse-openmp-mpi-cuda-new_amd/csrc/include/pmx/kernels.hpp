@@ -293,4 +293,19 @@ template <typename T>
 int launch_error_norms(const DevGeom& G, const DevTables& Tb, const T* w, const T* pa, double ca,
                        const T* pb, double cb, int npend, double* out, int max_blocks, hipStream_t s);
 
+// Device-resident user data (io_kernels.hip).  `src` / `out`: fp64 device arrays with row stride ld
+// elements and unit column stride.
+// rows x cols of src -> dst (row stride pitch), rounded to T as the host staging rounds
+template <typename T>
+void launch_scatter(const double* src, int64_t ld, T* dst, int64_t pitch, int rows, int cols, hipStream_t s);
+// *flag <- 1 if any of the rows x cols values is not finite (the caller zeroes it first)
+void launch_finite_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s);
+// local nodes (li0 .. li0+rows-1) x (lj0 .. lj0+cols-1) of a subdomain with local (0, 0) at global
+// (gi0, gj0) -> out[gi * ld + gj]: w + ca pa (+ cb pb) as launch_error_norms forms it (w, pa, pb point to
+// local (0, 0), row stride pitch); nodes on the global boundary (gi in {0, M}, gj in {0, N}) get zero
+template <typename T>
+void launch_gather(const T* w, const T* pa, double ca, const T* pb, double cb, int npend, int64_t pitch,
+                   double* out, int64_t ld, int li0, int lj0, int rows, int cols, int gi0, int gj0, int M, int N,
+                   hipStream_t s);
+
 }  // namespace pmx

@@ -39,6 +39,22 @@ struct SessionConfig {
   int sharing = 0;
 };
 
+// A global (M+1) x (N+1) fp64 field handed to a session: host memory, or memory of the session's
+// device.  ld: the row stride in elements (0: dense, N + 1); the column stride is 1.
+// A device field follows stream order without any synchronisation by the caller.  An input is read
+// after the work enqueued on `stream` (its producer's) before the call: the session records an event
+// there and its own streams wait for it.  An output is complete for work enqueued on `stream` after
+// the call: `stream` waits for an event of every session stream that wrote it.
+struct UserField {
+  const double* ptr = nullptr;
+  int64_t ld = 0;
+  bool on_device = false;
+  hipStream_t stream = nullptr;
+  UserField() = default;
+  UserField(const double* host) : ptr(host) {}  // a dense host array
+  explicit operator bool() const { return ptr != nullptr; }
+};
+
 class Session {
  public:
   explicit Session(const SessionConfig& cfg);
@@ -61,6 +77,19 @@ class Session {
   // sqrt(h1 h2 sum (B - A w)^2) over the interior for the w gather_local_w() returns, computed on the
   // device; B from `rhs` ((M+1) x (N+1), null: the constant F) under the ellipse mask.  world == 1.
   double residual_norm(const double* rhs = nullptr);
+  // The same three with either field in host or device memory (UserField).  A device field is checked
+  // for non-finite values on the device before anything of the session is written
+  // (std::invalid_argument, as the bindings raise for a host array), then read in place by the scatter
+  // kernel of every subdomain (io_kernels.hip): no staging buffer, nothing retained.  All three have
+  // consumed their inputs when they return.  Every subdomain must live on the field's device.
+  void init(const UserField& rhs, const UserField& w0);
+  RunStats solve(const UserField& rhs, const UserField& w0, int poll_batches = 1);
+  double residual_norm(const UserField& rhs);
+  // gather_local_w() into device memory: out[gi * ld + gj], (M+1) x (N+1) fp64 with row stride
+  // ld >= N + 1, bitwise the host gather -- pending w steps applied, boundary rows and columns zero;
+  // elements past column N of a row are not touched.  Stream order as UserField describes for an
+  // output on `consumer`; returns without waiting for the kernels.  Sessions that own every subdomain.
+  void gather_w_device(double* out, int64_t ld, hipStream_t consumer);
   void step(int64_t n);
   void synchronize();
   RunStats solve(int poll_batches = 1);
@@ -114,7 +143,13 @@ class Session {
   // to its rank's device) in threaded mode; the first exception is rethrown after all joined
   void for_drivers(const std::function<void(size_t, PcgDriver&)>& f);
   RunStats solve_impl(int poll_batches, bool do_init, int64_t every, const std::string& save_path);
-  void stage_init_data(const double* rhs, const double* w0);  // GpuSubdomainSolver::set_init_data on every solver
+  // GpuSubdomainSolver::set_init_data / set_init_data_device on every solver
+  void stage_init_data(const UserField& rhs, const UserField& w0);
+  void require_owns_all(const char* what) const;  // self / local communicator
+  int require_one_device() const;        // the device every solver lives on (device fields need one)
+  void wait_for(hipStream_t producer);   // every session stream waits for `producer`'s work so far
+  // throws std::invalid_argument naming the first device field with a non-finite value
+  void check_finite(const UserField& rhs, const UserField& w0);
 
   SessionConfig cfg_;
   ProcGrid pg_;

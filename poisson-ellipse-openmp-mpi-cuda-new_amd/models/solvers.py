@@ -31,7 +31,7 @@ class Result:
     status: str
     diff: float
     seconds: float                 # solver wall time (excludes setup where measurable)
-    w: Optional[np.ndarray] = None  # (M+1) x (N+1), boundary rows/cols zero
+    w: Optional[np.ndarray] = None  # (M+1) x (N+1), boundary rows/cols zero (hip, keep_solution="device": a tensor)
     backend: str = ""
     ranks: int = 1
     init_seconds: float = 0.0
@@ -48,7 +48,9 @@ class Result:
 def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
     """rhs / w0 (every backend): optional (M+1)x(N+1) float64 arrays -- a right-hand side f(x_i, y_j) in
     place of the constant F (the solver applies the ellipse mask: values outside D and on the box
-    boundary are ignored) and an initial iterate in place of w = 0."""
+    boundary are ignored) and an initial iterate in place of w = 0.  The hip backend also takes float64
+    tensors on its device for both and returns one with keep_solution="device" (solve_hip); every other
+    backend rejects device tensors."""
     if backend in ("cpu", "serial"):
         return solve_cpu(problem, threads=1, **kw)
     if backend in ("omp", "openmp"):
@@ -121,11 +123,19 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
 def solve_hip(problem: PoissonEllipse, ranks: int = 1, keep_solution: bool = True, poll_batches: int = 1,
               rhs=None, w0=None, **session_kw) -> Result:
     """rhs / w0: see solve(); the session uploads them for this solve and retains nothing
-    (Session.init(rhs=..., w0=...))."""
+    (Session.init(rhs=..., w0=...)).  Here they may also be float64 tensors on the session's device
+    (any object with __cuda_array_interface__): kernels read them in place, after the work already
+    enqueued on the current torch stream, with no synchronisation by the caller.
+
+    keep_solution: True -- Result.w is a NumPy array; "device" -- a torch.float64 tensor on the session's
+    device (Session.w_tensor(): no pass through the host, usable at once on the current torch stream);
+    False -- None."""
+    if not isinstance(keep_solution, bool) and keep_solution != "device":
+        raise ValueError(f"keep_solution must be True, False or 'device', got {keep_solution!r}")
     t0 = time.perf_counter()
     s = make_session(problem, ranks=ranks, **session_kw)
     st = s.solve(poll_batches, rhs=rhs, w0=w0)
-    w = s.gather_local_w() if keep_solution else None
+    w = s.w_tensor() if keep_solution == "device" else s.gather_local_w() if keep_solution else None
     r = Result(st["iters"], st["status"], st["diff"], st["solve_seconds"], w, backend="hip", ranks=ranks,
                init_seconds=st["init_seconds"],
                extra=dict(launched=st["launched"], nan=st["nan"], setup_seconds=time.perf_counter() - t0,

@@ -38,6 +38,7 @@ HIP_SOURCES = [
     "hip/pcg1_block.hip",
     "hip/ca_kernels.hip",
     "hip/ops_kernels.hip",
+    "hip/io_kernels.hip",
     "hip/gpu_solver.hip",
     "hip/pcg_driver.hip",
     "hip/ca_solver.hip",
