@@ -5,7 +5,7 @@
 // (ellipse x^2+4y^2<1, delta=1e-6, max_iter=(M-1)(N-1), weighted norm).  The superset:
 //
 //   pmx [M N] [--ax 1.0 --by 0.5] [--box -1,1,-0.6,0.6] [--f 1.0] [--delta 1e-6] [--max-iter K]
-//       [--breakdown-tol 1e-15]
+//       [--breakdown-tol 1e-15] [--sigma 0]
 //       [--backend cpu|omp|hip] [--threads T] [--ranks P] [--gpus G] [--comm self|local|rccl]
 //       [--split reference|auto|rows|cols] [--dtype fp64|fp32|mixed] [--norm weighted|unweighted]
 //       [--exact] [--graph-batch 32] [--tile-rows 0] [--kernel wave] [--vec 2] [--waves 4]
@@ -51,7 +51,7 @@ struct Cli {
 [[noreturn]] void usage(const char* msg) {
   if (msg) std::cerr << "pmx: " << msg << "\n";
   std::cerr << "usage: pmx [M N] [--ax A] [--by B] [--box a1,b1,a2,b2] [--f F] [--delta D] [--max-iter K]\n"
-               "           [--breakdown-tol T]\n"
+               "           [--breakdown-tol T] [--sigma S]\n"
                "           [--backend cpu|omp|hip] [--threads T] [--ranks P] [--gpus G]\n"
                "           [--comm self|local|rccl] [--split reference|auto|rows|cols]\n"
                "           [--dtype fp64|fp32|mixed] [--norm weighted|unweighted] [--exact]\n"
@@ -90,6 +90,7 @@ Cli parse(int argc, char** argv) {
     else if (a == "--delta") c.spec.delta = std::atof(val().c_str());
     else if (a == "--breakdown-tol") c.spec.breakdown_tol = std::atof(val().c_str());
     else if (a == "--max-iter") c.spec.max_iter = std::atoll(val().c_str());
+    else if (a == "--sigma") c.spec.sigma = std::atof(val().c_str());  // (-Δ + sigma) u = f, sigma >= 0
     else if (a == "--box") {
       const std::string v = val();
       if (std::sscanf(v.c_str(), "%lf,%lf,%lf,%lf", &c.spec.A1, &c.spec.B1, &c.spec.A2, &c.spec.B2) != 4)
@@ -231,8 +232,10 @@ int run_cpu(Cli& c, double t_prog, bool header = true, bool footer = true) {
     JsonLine j;
     j.ks("backend", c.backend).kv("M", s.M).kv("N", s.N).kv("ranks", c.ranks).kv("threads", threads)
         .kv("iters", r.iters).ks("status", status_name(r.status)).kv("seconds", r.seconds)
-        .kv("mlups", double(s.M - 1) * (s.N - 1) * r.iters / r.seconds / 1e6).kv("l2_error", e.l2)
-        .kv("max_error", e.max_err).kv("max_w", e.max_w).kv("total_seconds", now() - t_prog);
+        .kv("mlups", double(s.M - 1) * (s.N - 1) * r.iters / r.seconds / 1e6);
+    // the closed-form solution the errors compare with holds for sigma = 0 only
+    if (s.sigma == 0.0) j.kv("l2_error", e.l2).kv("max_error", e.max_err);
+    j.kv("max_w", e.max_w).kv("sigma", s.sigma).kv("total_seconds", now() - t_prog);
     std::cout << j.str() << std::endl;
   }
   return 0;
@@ -350,8 +353,9 @@ int run_hip(Cli& c, double t_prog) {
         .ks("status", status_name(st.status)).kv("solve_seconds", st.solve_seconds)
         .kv("init_seconds", st.init_seconds)
         .kv("mlups", double(s.M - 1) * (s.N - 1) * st.iters / st.solve_seconds / 1e6)
-        .kv("us_per_iter", st.solve_seconds / std::max<int64_t>(1, st.iters) * 1e6)
-        .kv("l2_error", e.l2).kv("max_error", e.max_err).kv("max_w", e.max_w)
+        .kv("us_per_iter", st.solve_seconds / std::max<int64_t>(1, st.iters) * 1e6);
+    if (s.sigma == 0.0) j.kv("l2_error", e.l2).kv("max_error", e.max_err);  // (closed form: sigma = 0 only)
+    j.kv("max_w", e.max_w).kv("sigma", s.sigma)
         .kv("device_bytes", sess.device_bytes()).kv("total_seconds", now() - t_prog);
     if (c.profile > 0)
       j.kv("profiled_iters", c.profile).kv("phase_kernel_a_s", ph.t_kernel_a)

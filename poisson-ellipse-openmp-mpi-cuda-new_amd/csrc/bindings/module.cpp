@@ -135,6 +135,14 @@ SessionField session_field(const py::object& obj, Session& s, const std::string&
   return r;
 }
 
+// The Python-orchestrated paths (OpContext ops, SubdomainSolver + comm_layout under DistGpuPCG
+// comm="torch") evaluate -div(k grad u) alone: ValueError for the screened problem.
+void refuse_sigma(const ProblemSpec& s, const char* what) {
+  if (s.sigma != 0.0)
+    throw py::value_error(std::string(what) + " is not built for sigma != 0 (the screened problem): use a native "
+                          "Session (solve(..., \"hip\"), make_session, DistGpuPCG comm=\"native\")");
+}
+
 py::dict sd_dict(const Subdomain& s) {
   py::dict d;
   d["M"] = s.M; d["N"] = s.N; d["Px"] = s.grid.Px; d["Py"] = s.grid.Py;
@@ -236,6 +244,7 @@ class OpContext {
   OpContext(const ProblemSpec& spec, int Px, int Py, int rank, int64_t pitch, int device)
       : spec_(spec), device_(device) {
     spec_.validate();
+    refuse_sigma(spec_, "DeviceOps / OpContext");
     HIP_CHECK(hipSetDevice(device));
     sd_ = decompose_2d(spec.M, spec.N, ProcGrid{Px, Py}, rank);
     PMX_CHECK(pitch >= sd_.ny + 2, "pitch " << pitch << " < ny+2 = " << sd_.ny + 2);
@@ -344,6 +353,7 @@ PYBIND11_MODULE(_pmx, m) {
       .def_readwrite("ax", &ProblemSpec::ax).def_readwrite("by", &ProblemSpec::by)
       .def_readwrite("F", &ProblemSpec::F).def_readwrite("delta", &ProblemSpec::delta)
       .def_readwrite("breakdown_tol", &ProblemSpec::breakdown_tol)
+      .def_readwrite("sigma", &ProblemSpec::sigma)
       .def_readwrite("max_iter", &ProblemSpec::max_iter).def_readwrite("norm", &ProblemSpec::norm)
       .def("effective_max_iter", &ProblemSpec::effective_max_iter)
       .def("validate", &ProblemSpec::validate);
@@ -445,6 +455,7 @@ PYBIND11_MODULE(_pmx, m) {
   // pass the returned "algo" on to SubdomainSolver(algo=...).
   m.def("comm_layout", [](const ProblemSpec& s, int Px, int Py, int rank, const std::string& dtype,
                           const std::string& kernel, bool exact, int device, int algo, int sharing) {
+          refuse_sigma(s, "comm_layout (the Python-orchestrated solver)");
           GpuOptions o = make_options(device, kernel, 256, 0, 4, 0, dtype, exact, 0, false);
           o.algo = algo;
           o = resolve_options(o);
@@ -496,7 +507,9 @@ PYBIND11_MODULE(_pmx, m) {
     GpuOptions o = make_options(0, "wave", 256, 0, 4, 0, dtype, exact, 32, false);
     o.algo = algo;
     o = resolve_options(o);
-    return choose_algo(s, make_process_grid(world, s.M, s.N, split), o, device_bytes, std::max(1, per_device), true);
+    const ProcGrid pg = make_process_grid(world, s.M, s.N, split);
+    apply_sigma_rules(s, pg, o);
+    return choose_algo(s, pg, o, device_bytes, std::max(1, per_device), true);
   }, py::arg("spec"), py::arg("world") = 1, py::arg("split") = Split::kAuto, py::arg("dtype") = "fp64",
      py::arg("device_bytes") = 0.0, py::arg("per_device") = 1, py::arg("algo") = -1, py::arg("exact") = false);
   m.def("estimate_device_bytes", [](const ProblemSpec& s, int world, Split split, int rank, const std::string& dtype,
@@ -521,6 +534,7 @@ PYBIND11_MODULE(_pmx, m) {
                        const std::string& kernel, int block, int vec, int waves, int tile_rows,
                        const std::string& dtype, bool exact, uintptr_t arena, bool check, int vec_b,
                        int waves_b, int tile_rows_b, bool b_ring, int algo) {
+             refuse_sigma(s, "SubdomainSolver (the Python-orchestrated solver)");
              const Subdomain sd = decompose_2d(s.M, s.N, ProcGrid{Px, Py}, rank);
              return std::make_unique<GpuSubdomainSolver>(
                  s, sd, make_options(device, kernel, block, vec, waves, tile_rows, dtype, exact, 0, check,
@@ -691,7 +705,8 @@ PYBIND11_MODULE(_pmx, m) {
              py::gil_scoped_release g;
              return s.residual_norm(f.f);
            }, py::arg("rhs") = py::none(),
-           "sqrt(h1 h2 sum (B - A w)^2) of the current w, computed on the device (world == 1); rhs as in init "
+           "sqrt(h1 h2 sum (B - A w)^2) of the current w (A + sigma I with sigma != 0), computed on the device "
+           "(world == 1); rhs as in init "
            "(a device array is ordered after its producer's stream and read in place)")
       .def("gather_w_device", [](Session& s, py::object out) {
              const UserField o = device_field(out, s.solver(0).spec(), s.solver(0).device(), "out", true);
@@ -789,6 +804,7 @@ PYBIND11_MODULE(_pmx, m) {
       .def("subdomain", [](Session& s, int i) { return sd_dict(s.solver(i).sd()); }, py::arg("i") = 0)
       .def_property_readonly("num_local", &Session::num_local)
       .def_property_readonly("comm_name", &Session::comm_name)
+      .def_property_readonly("algo_name", &Session::algo_name)
       .def_property_readonly("overlapped", [](Session& s) { return s.overlapped(); })
       .def_property_readonly("poisoned", [](Session& s) { return s.poisoned(); })
       .def_property_readonly("device_bytes", &Session::device_bytes)

@@ -65,6 +65,7 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
   const int P = N + 2;  // pitch; arrays (M+2) x (N+2), index i*P + j
   const size_t n = size_t(M + 2) * P;
   const double h1 = g.h1, h2 = g.h2;
+  const double sigma = spec.sigma;  // screened problem: A + sigma I, D + sigma (0: the reference's operator)
   const int nt = threads < 1 ? 1 : threads;
   (void)nt;
 
@@ -95,7 +96,7 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
     for (int i = 1; i <= M - 1; ++i)
       for (int j = 1; j <= N - 1; ++j) {
         const size_t c = size_t(i) * P + j;
-        const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2);
+        const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + sigma;
         z[c] = (D != 0.0) ? r[c] / D : 0.0;
       }
   };
@@ -106,7 +107,7 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
         const size_t c = size_t(i) * P + j;
         const double Ax = -1.0 / h1 * (a[c + P] * (p[c + P] - p[c]) / h1 - a[c] * (p[c] - p[c - P]) / h1);
         const double Ay = -1.0 / h2 * (b[c + 1] * (p[c + 1] - p[c]) / h2 - b[c] * (p[c] - p[c - 1]) / h2);
-        Ap[c] = Ax + Ay;
+        Ap[c] = sigma != 0.0 ? (Ax + Ay) + sigma * p[c] : Ax + Ay;
       }
   };
 
@@ -220,7 +221,7 @@ double CpuSubdomain::init() {
 
 double CpuSubdomain::matvec_dot() {
   const int nx = sd_.nx, ny = sd_.ny, P = ny + 2, nt = threads_;
-  const double h1 = g_.h1, h2 = g_.h2;
+  const double h1 = g_.h1, h2 = g_.h2, sigma = spec_.sigma;
   const double* a = a_.data(); const double* b = b_.data(); const double* p = p_.data();
   double* Ap = Ap_.data();
   double sum = 0.0;
@@ -230,7 +231,7 @@ double CpuSubdomain::matvec_dot() {
       const size_t c = size_t(li) * P + lj;
       const double Ax = -1.0 / h1 * (a[c + P] * (p[c + P] - p[c]) / h1 - a[c] * (p[c] - p[c - P]) / h1);
       const double Ay = -1.0 / h2 * (b[c + 1] * (p[c + 1] - p[c]) / h2 - b[c] * (p[c] - p[c - 1]) / h2);
-      Ap[c] = Ax + Ay;
+      Ap[c] = sigma != 0.0 ? (Ax + Ay) + sigma * p[c] : Ax + Ay;
       sum += Ap[c] * p[c];
     }
   return sum * h1 * h2;
@@ -256,7 +257,7 @@ void CpuSubdomain::update_wr(double alpha, double* diff_local) {
 
 double CpuSubdomain::precond_dot() {
   const int nx = sd_.nx, ny = sd_.ny, P = ny + 2, nt = threads_;
-  const double h1 = g_.h1, h2 = g_.h2;
+  const double h1 = g_.h1, h2 = g_.h2, sigma = spec_.sigma;
   const double* a = a_.data(); const double* b = b_.data(); const double* r = r_.data();
   double* z = z_.data();
   double sum = 0.0;
@@ -264,7 +265,7 @@ double CpuSubdomain::precond_dot() {
   for (int li = 1; li <= nx; ++li)
     for (int lj = 1; lj <= ny; ++lj) {
       const size_t c = size_t(li) * P + lj;
-      const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2);
+      const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + sigma;
       z[c] = (D != 0.0) ? r[c] / D : 0.0;
       sum += z[c] * r[c];
     }

@@ -100,6 +100,7 @@ struct Pcg1Part {
   int tiles_i, ti_lo, ti_hi, tj_lo, tj_hi;
   const Pcg1Slot* order;  // position -> tile + row classes (pcg1_build_order), or nullptr: pcg1_tile's order
   int count;         // tiles of this launch
+  double sigma;      // ProblemSpec::sigma, read by the SH sweeps only (last, after everything a sweep reads)
 };
 
 // k-th tile of the part -> (ti, tj); false past the end.  The frame is enumerated as: tile rows
@@ -131,7 +132,9 @@ __host__ __device__ inline bool pcg1_tile(int k, const Pcg1Part& P, int tiles_j,
   return false;
 }
 
-template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int DPF = 0>
+// SH: the sweep of the screened problem (ProblemSpec::sigma != 0; pcg1_march.hpp) -- A + sigma I and
+// D + sigma, sigma from Pcg1Part.  launch_pcg1 picks it; SH = false is the sweep of every other solve.
+template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int DPF = 0, bool SH = false>
 __global__ void __launch_bounds__(64 * WAVES, (pcg1_min_waves<T, C, VEC, WAVES, PF, WS>()))
 k_pcg1(DevGeom G, DevTables Tb, T* __restrict__ w, T* r, T* r2, T* p0, T* p1,
        double* __restrict__ partials, PcgState* S, int TI, int tiles_j, int ntiles, Pcg1Part part) {
@@ -183,18 +186,19 @@ k_pcg1(DevGeom G, DevTables Tb, T* __restrict__ w, T* r, T* r2, T* p0, T* p1,
   const bool fast = VEC == 2 && j1 == j0 + WO - 1 && G.gi0 + i0 - 2 >= 1 && G.gi0 + i1 + 2 <= G.M - 1 &&
                     G.gj0 + j0 - 2 >= 1 && G.gj0 + j0 + 64 * VEC - 3 <= G.N - 1;
   const bool use_cls = part.order != nullptr && TI + 5 <= 64 / 2;  // 2 bits for each of the TI+5 rows
-  const ArithF AF{float(G.cx), float(G.cy), float(G.dinv_in), float(G.dinv_out), float(G.inv_eps)};
+  const ArithF AF{float(G.cx), float(G.cy), float(G.dinv_in), float(G.dinv_out), float(G.inv_eps),
+                  SH ? float(part.sigma) : 0.0f, SH ? part.sigma : 0.0};
 #define PMX_MARCH(E, F)                                                                                       \
-  pcg1_march<T, C, VEC, PF, E, F, 0, (WAVES > 1)>(G, Tb, AF, w, rold, rnew, pold, pnew, i0, i1, j0, j1, alpha, beta, \
-                                                c1, c2, acc, scol, ocls, use_cls)
+  pcg1_march<T, C, VEC, PF, E, F, 0, (WAVES > 1), SH>(G, Tb, AF, w, rold, rnew, pold, pnew, i0, i1, j0, j1, alpha, \
+                                                    beta, c1, c2, acc, scol, ocls, use_cls)
   // LDS-DMA ring of the FAST march (pcg1_march's DPF mode): DPF slots of r, p (, w) rows per wave
   constexpr int kRingDoubles = DPF > 0 ? DPF * (WS ? 3 : 2) * 128 : 2;
   __shared__ double s_ring[WAVES * kRingDoubles];
   double* dring = s_ring + __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)) * kRingDoubles;
   (void)dring;
 #define PMX_MARCH_D(E)                                                                                            \
-  pcg1_march<T, C, VEC, PF, E, true, DPF>(G, Tb, AF, w, rold, rnew, pold, pnew, i0, i1, j0, j1, alpha, beta, c1, c2, \
-                                          acc, scol, ocls, use_cls, dring)
+  pcg1_march<T, C, VEC, PF, E, true, DPF, false, SH>(G, Tb, AF, w, rold, rnew, pold, pnew, i0, i1, j0, j1, alpha, beta, \
+                                                     c1, c2, acc, scol, ocls, use_cls, dring)
 #define PMX_MARCH_W(F)                                     \
   if constexpr (!WS) {                                     \
     PMX_MARCH(0, F);                                       \
@@ -464,7 +468,7 @@ int pcg1_build_order(const DevGeom& G, const DevTables& Tb, TileCfg& tc, Pcg1Slo
   std::vector<Pcg1Slot> order(3 * per, Pcg1Slot{-1, 0, 0ull});
   int nslow = 0;
   for (int part = 0; part <= 2; ++part) {
-    const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, nullptr, 0};
+    const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, nullptr, 0, 0.0};
     const int count = part == 0 ? n : part == 1 ? tc.interior_tiles() : n - tc.interior_tiles();
     // groups: runs of up to gw consecutive tiles of the part's enumeration within one tile row
     std::vector<std::vector<int>> groups;
@@ -572,7 +576,8 @@ int pcg1_lds_pad(int wpcu, int waves) {
 
 template <typename T>
 void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0, T* p1,
-                 double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part, bool wsweep) {
+                 double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part, bool wsweep,
+                 double sigma) {
   PMX_CHECK(tc.kind == 3, "launch_pcg1 needs make_pcg1_tiles");
   PMX_CHECK(part >= 0 && part <= 2, "launch_pcg1: part must be 0, 1 or 2");
   const int tiles = part == 0 ? tc.ntiles() : part == 1 ? tc.interior_tiles() : tc.ntiles() - tc.interior_tiles();
@@ -582,7 +587,7 @@ void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0
   PMX_CHECK(tc.waves == 1 || grouped, "pcg1: workgroups of several waves need the grouped dispatch order");
   const int nb = grouped ? tc.groups[part] : tiles;
   const int count = grouped ? nb * tc.waves : tiles;
-  const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, ord, count};
+  const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, ord, count, sigma};
   if (tiles == 0) return;
   PMX_CHECK(G.nb == 0 || (G.nx >= 2 && G.ny >= 2), "pcg1 on a decomposed grid needs subdomains >= 2 x 2");
   const int bs = 64 * tc.waves;
@@ -605,6 +610,37 @@ void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0
     PMX_CHECK(tc.dpf == 0, "pcg1: the LDS-DMA march needs fp64, VEC 2 x 1 wave, prefetch 1 and dpf 2 or 3"); \
     PMX_PCG1_CD(C, V, WV, PF, 0);                                                                        \
   } while (0)
+  // the screened problem's sweeps (SH): the shapes the library picks on its own -- VEC 2, 1 wave,
+  // register prefetch 1 or 2
+#define PMX_PCG1_SH(C, PF)                                                                               \
+  do {                                                                                                   \
+    if (wsweep)                                                                                          \
+      hipLaunchKernelGGL((k_pcg1<T, C, 2, 1, PF, true, 0, true>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, \
+                         r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);                  \
+    else                                                                                                 \
+      hipLaunchKernelGGL((k_pcg1<T, C, 2, 1, PF, false, 0, true>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, \
+                         r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);                  \
+  } while (0)
+  if (sigma != 0.0) {
+    PMX_CHECK(tc.vec == 2 && tc.waves == 1 && (tc.pf == 1 || tc.pf == 2) && tc.dpf == 0,
+              "pcg1 with sigma != 0 runs the default tile shapes (vec 2 x 1 wave, prefetch 1 or 2, no LDS-DMA)");
+    bool f32 = false;
+    if constexpr (std::is_same_v<T, float>) f32 = tc.arith32 != 0;
+    PMX_CHECK(!tc.arith32 || f32, "pcg1: fp32 arithmetic needs fp32 storage");
+    if (f32) {
+      if constexpr (std::is_same_v<T, float>) {
+        if (tc.pf == 1) PMX_PCG1_SH(float, 1);
+        else PMX_PCG1_SH(float, 2);
+      }
+    } else if (tc.pf == 1) {
+      PMX_PCG1_SH(double, 1);
+    } else {
+      PMX_PCG1_SH(double, 2);
+    }
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+#undef PMX_PCG1_SH
   // fp32 arithmetic: fp32 storage only, the default tile shape (VEC 2, 1 wave) and prefetch 1-3
 #define PMX_PCG1(V, WV, PF)                                                                              \
   do {                                                                                                   \
@@ -676,12 +712,12 @@ void* pcg1_wave_trace_setup(long long it, int nwaves) {
 #endif
 
 template void launch_pcg1<double>(const DevGeom&, const DevTables&, double*, double*, double*, double*,
-                                  double*, double*, PcgState*, const TileCfg&, hipStream_t, int, bool);
+                                  double*, double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double);
 template void launch_pcg1_halo<double>(const DevGeom&, double*, double*, double*, double*, HaloBufs<double>,
                                         long long, bool, hipStream_t, long long*);
 template void launch_pcg1_halo<float>(const DevGeom&, float*, float*, float*, float*, HaloBufs<float>,
                                        long long, bool, hipStream_t, long long*);
 template void launch_pcg1<float>(const DevGeom&, const DevTables&, float*, float*, float*, float*, float*,
-                                 double*, PcgState*, const TileCfg&, hipStream_t, int, bool);
+                                 double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double);
 
 }  // namespace pmx

@@ -267,6 +267,10 @@ __device__ __forceinline__ void coef(const RowCo& c, const DevTables& Tb, const 
 // sweep is issue-bound in fp64 arithmetic (profiles/r3/kernel_ab/pmc_fp32_16384.md).
 struct ArithF {
   float cx, cy, dinv_in, dinv_out, inv_eps;
+  // SH sweeps only (see zdiv_c): sigma in both compute types; dinv_in / dinv_out then include it, as
+  // DevGeom's do
+  float sigma;
+  double sigma_d;
 };
 
 __device__ __forceinline__ double fma_c(double a, double b, double c) { return __builtin_fma(a, b, c); }
@@ -288,10 +292,15 @@ __device__ __forceinline__ void coef_c(const RowCo& c, const DevTables& Tb, cons
   }
 }
 
-template <typename C>
+// SH (zdiv_c, apply_c, apply_row, pcg1_march): the screened problem (-div(k grad u) + sigma u = f).  Every
+// A x gains + sigma x_centre as one explicit FMA after the unshifted expression, every D gains + sigma; the
+// two precomputed reciprocals of the uniform rows arrive with sigma included.  Nothing else differs, and
+// SH = false is the code of every sweep without it.
+template <typename C, bool SH = false>
 __device__ __forceinline__ C zdiv_c(int ucls, C r, C a0, C a1, C b0, C b1, const DevGeom& G, const ArithF& F) {
   if constexpr (std::is_same_v<C, double>) {
-    return zdiv_u<false>(ucls, r, a0, a1, b0, b1, G);
+    if constexpr (SH) return zdiv_u_sh(ucls, r, a0, a1, b0, b1, G, F.sigma_d);
+    else return zdiv_u<false>(ucls, r, a0, a1, b0, b1, G);
   } else {
     if (ucls == 1) return r * F.dinv_in;
     if (ucls == 2) return r * F.dinv_out;
@@ -299,26 +308,31 @@ __device__ __forceinline__ C zdiv_c(int ucls, C r, C a0, C a1, C b0, C b1, const
     const bool out = (a0 == F.inv_eps) & (a1 == F.inv_eps) & (b0 == F.inv_eps) & (b1 == F.inv_eps);
     if (in) return r * F.dinv_in;
     if (out) return r * F.dinv_out;
-    return r / __builtin_fmaf(a1 + a0, F.cx, (b1 + b0) * F.cy);
+    const float D = __builtin_fmaf(a1 + a0, F.cx, (b1 + b0) * F.cy);
+    if constexpr (SH) return r / (D + F.sigma);
+    else return r / D;
   }
 }
 
-template <typename C>
+template <typename C, bool SH = false>
 __device__ __forceinline__ C apply_c(C pc, C pim, C pip, C pjm, C pjp, C a0, C a1, C b0, C b1, const DevGeom& G,
                                      const ArithF& F) {
   if constexpr (std::is_same_v<C, double>) {
-    return apply_a<false>(pc, pim, pip, pjm, pjp, a0, a1, b0, b1, G);
+    if constexpr (SH) return apply_a_sh<false>(pc, pim, pip, pjm, pjp, a0, a1, b0, b1, G, F.sigma_d);
+    else return apply_a<false>(pc, pim, pip, pjm, pjp, a0, a1, b0, b1, G);
   } else {
     const float x = __builtin_fmaf(a1, pc - pip, a0 * (pc - pim));
     const float y = __builtin_fmaf(b1, pc - pjp, b0 * (pc - pjm));
-    return __builtin_fmaf(F.cx, x, F.cy * y);
+    const float Ap = __builtin_fmaf(F.cx, x, F.cy * y);
+    if constexpr (SH) return __builtin_fmaf(F.sigma, pc, Ap);
+    else return Ap;
   }
 }
 
 // A x on the VEC columns of a lane: centre xc, rows i-1 / i+1 xim / xip, the lane neighbours'
 // edge columns left / right (DPP).  fp32 with VEC = 2: both columns in packed fp32 (v_pk_*), the
 // same per-column fmaf sequence as apply_c (bit-identical results).
-template <typename C, int VEC>
+template <typename C, int VEC, bool SH = false>
 __device__ __forceinline__ void apply_row(const C (&xc)[VEC], const C (&xim)[VEC], const C (&xip)[VEC], C left,
                                           C right, const C (&a0)[VEC], const C (&a1)[VEC], const C (&b0)[VEC],
                                           const C (&b1)[VEC], const DevGeom& G, const ArithF& F, C (&out)[VEC]) {
@@ -330,14 +344,18 @@ __device__ __forceinline__ void apply_row(const C (&xc)[VEC], const C (&xim)[VEC
     const f2 x = __builtin_elementwise_fma(A1, pc - pip, A0 * (pc - pim));
     const f2 y = __builtin_elementwise_fma(B1, pc - pjp, B0 * (pc - pjm));
     const f2 cx = {F.cx, F.cx}, cy = {F.cy, F.cy};
-    const f2 r = __builtin_elementwise_fma(cx, x, cy * y);
+    f2 r = __builtin_elementwise_fma(cx, x, cy * y);
+    if constexpr (SH) {
+      const f2 sg = {F.sigma, F.sigma};
+      r = __builtin_elementwise_fma(sg, pc, r);
+    }
     out[0] = r.x;
     out[1] = r.y;
   } else {
 #pragma unroll
     for (int u = 0; u < VEC; ++u)
-      out[u] = apply_c<C>(xc[u], xim[u], xip[u], u == 0 ? left : xc[u - 1], u == VEC - 1 ? right : xc[u + 1], a0[u],
-                          a1[u], b0[u], b1[u], G, F);
+      out[u] = apply_c<C, SH>(xc[u], xim[u], xip[u], u == 0 ? left : xc[u - 1], u == VEC - 1 ? right : xc[u + 1],
+                              a0[u], a1[u], b0[u], b1[u], G, F);
   }
 }
 
@@ -405,7 +423,7 @@ struct Pcg1Row {
 // pieces at different times (bench/probe/dma_march.hip k_lock: 16384^2, 16 waves per CU, 1.846 ->
 // 1.688 ms per sweep).  Pure pacing: no data passes between the waves, every wave of a workgroup
 // marches the same number of rows (one tile row), and a wave that has left no longer counts.
-template <typename T, typename C, int VEC, int PF, int WM, bool FAST, int DPF = 0, bool LOCK = false>
+template <typename T, typename C, int VEC, int PF, int WM, bool FAST, int DPF = 0, bool LOCK = false, bool SH = false>
 __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb, const ArithF& F, T* __restrict__ w,
                                            const T* __restrict__ rold, T* __restrict__ rnew,
                                            const T* __restrict__ pold,
@@ -498,7 +516,7 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       pom[u] = in ? C(cur.p[u]) : C(0);
       C a0, a1, b0, b1;
       coef_c<C>(cA, Tb, G, F, scol, u, lane, gj[u], a0, a1, b0, b1);
-      const C z = zdiv_c<C>(cA.ucls, rom[u], a0, a1, b0, b1, G, F);
+      const C z = zdiv_c<C, SH>(cA.ucls, rom[u], a0, a1, b0, b1, G, F);
       const C v = fma_c(beta, pom[u], z);
       Pm[u] = in ? C(static_cast<T>(v)) : C(0);  // the stored (rounded) p^k is the one used
     }
@@ -523,33 +541,33 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       if constexpr (PK) {
 #pragma unroll
         for (int u = 0; u < VEC; ++u) coef_at(cB, mb, u, a0[u], a1[u], b0[u], b1[u]);
-        apply_row<C, VEC>(Pm1, Pm2, Pm, left, right, a0, a1, b0, b1, G, F, Ap);
+        apply_row<C, VEC, SH>(Pm1, Pm2, Pm, left, right, a0, a1, b0, b1, G, F, Ap);
         // p^{k-2} recovery (WM 2): A p^{k-1}
         if constexpr (WM == 2)
-          apply_row<C, VEC>(po1, po2, pom, oleft, oright, a0, a1, b0, b1, G, F, Apo);
+          apply_row<C, VEC, SH>(po1, po2, pom, oleft, oright, a0, a1, b0, b1, G, F, Apo);
       }
 #pragma unroll
       for (int u = 0; u < VEC; ++u) {
         if constexpr (!PK) {
           coef_at(cB, mb, u, a0[u], a1[u], b0[u], b1[u]);
-          Ap[u] = apply_c<C>(Pm1[u], Pm2[u], Pm[u], u == 0 ? left : Pm1[u - 1],
+          Ap[u] = apply_c<C, SH>(Pm1[u], Pm2[u], Pm[u], u == 0 ? left : Pm1[u - 1],
                              u == VEC - 1 ? right : Pm1[u + 1], a0[u], a1[u], b0[u], b1[u], G, F);
           if constexpr (WM == 2)
-            Apo[u] = apply_c<C>(po1[u], po2[u], pom[u],
+            Apo[u] = apply_c<C, SH>(po1[u], po2[u], pom[u],
                                 u == 0 ? oleft : po1[u - 1], u == VEC - 1 ? oright : po1[u + 1], a0[u], a1[u], b0[u],
                                 b1[u], G, F);
         }
         const bool in = FAST || (rowB && colin[u]);
         const C rn = C(static_cast<T>(fma_c(-alpha, Ap[u], ro1[u])));  // = upd_r<false>
         rs[u] = static_cast<T>(in ? rn : C(0));
-        const C zn = zdiv_c<C>(cB.ucls, rn, a0[u], a1[u], b0[u], b1[u], G, F);
+        const C zn = zdiv_c<C, SH>(cB.ucls, rn, a0[u], a1[u], b0[u], b1[u], G, F);
         Zm1[u] = in ? zn : C(0);
         ps[u] = static_cast<T>(Pm1[u]);
         if constexpr (WM == 1) {
           ws[u] = static_cast<T>(fma_c(alpha, Pm1[u], fma_c(c1, po1[u], C(cur.w[u]))));
         } else if constexpr (WM == 2) {
           // r^{k-2} = r^{k-1} + alpha_{k-1} A p^{k-1};  p^{k-2} = (p^{k-1} - D^-1 r^{k-2}) / beta_{k-1}
-          const C zo = zdiv_c<C>(cB.ucls, fma_c(c1, Apo[u], ro1[u]), a0[u], a1[u], b0[u], b1[u], G, F);
+          const C zo = zdiv_c<C, SH>(cB.ucls, fma_c(c1, Apo[u], ro1[u]), a0[u], a1[u], b0[u], b1[u], G, F);
           const C t = fma_c(c2, po1[u] - zo, C(cur.w[u]));
           ws[u] = static_cast<T>(fma_c(alpha, Pm1[u], fma_c(c1, po1[u], t)));
         } else if constexpr (WM == 3) {
@@ -578,13 +596,13 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       if constexpr (PK) {
 #pragma unroll
         for (int u = 0; u < VEC; ++u) coef_at(cC, mcr, u, a0[u], a1[u], b0[u], b1[u]);
-        apply_row<C, VEC>(Zm2, Zm3, Zm1, left, right, a0, a1, b0, b1, G, F, Az);
+        apply_row<C, VEC, SH>(Zm2, Zm3, Zm1, left, right, a0, a1, b0, b1, G, F, Az);
       }
 #pragma unroll
       for (int u = 0; u < VEC; ++u) {
         if constexpr (!PK) {
           coef_at(cC, mcr, u, a0[u], a1[u], b0[u], b1[u]);
-          Az[u] = apply_c<C>(Zm2[u], Zm3[u], Zm1[u], u == 0 ? left : Zm2[u - 1],
+          Az[u] = apply_c<C, SH>(Zm2[u], Zm3[u], Zm1[u], u == 0 ? left : Zm2[u - 1],
                              u == VEC - 1 ? right : Zm2[u + 1], a0[u], a1[u], b0[u], b1[u], G, F);
         }
         if (FAST || own[u]) {

@@ -184,6 +184,30 @@ __device__ __forceinline__ double apply_a(double pc, double pim, double pip, dou
   }
 }
 
+// The screened problem (ProblemSpec::sigma; the SH kernels k_pcg1 / k_init): (A + sigma I) p as ONE explicit
+// FMA after the unshifted expression, so every call site agrees bitwise, and z = r / (D + sigma) -- the two
+// precomputed reciprocals of the uniform stencils (DevGeom::dinv_in / dinv_out) already include sigma.
+template <bool EXACT>
+__device__ __forceinline__ double apply_a_sh(double pc, double pim, double pip, double pjm, double pjp,
+                                             double a0, double a1, double b0, double b1,
+                                             const DevGeom& G, double sigma) {
+  return __builtin_fma(sigma, pc, apply_a<EXACT>(pc, pim, pip, pjm, pjp, a0, a1, b0, b1, G));
+}
+__device__ __forceinline__ double add_sigma(double D, double sigma) {
+  PMX_NO_CONTRACT
+  return D + sigma;
+}
+__device__ __forceinline__ double zdiv_u_sh(int ucls, double r, double a0, double a1, double b0, double b1,
+                                            const DevGeom& G, double sigma) {
+  if (ucls == 1) return r * G.dinv_in;
+  if (ucls == 2) return r * G.dinv_out;
+  const bool in = (a0 == 1.0) & (a1 == 1.0) & (b0 == 1.0) & (b1 == 1.0);
+  const bool out = (a0 == G.inv_eps) & (a1 == G.inv_eps) & (b0 == G.inv_eps) & (b1 == G.inv_eps);
+  if (in) return r * G.dinv_in;
+  if (out) return r * G.dinv_out;
+  return r / add_sigma(diag<false>(a0, a1, b0, b1, G), sigma);
+}
+
 // w + alpha p and r - alpha A p.  EXACT: the reference's separate multiply and add
 // (stage0/Withoutopenmp1.cpp:135-143); fast: one explicit FMA each, so the r values packed for the
 // halo by k_edge_r equal those k_pcg_b stores.

@@ -53,13 +53,15 @@ TileCfg make_tiles(const DevGeom& G, int block, int rows) {
 // its pending steps applied as k_error_norms applies them, f from X.f (nullptr: G.F).
 // Each thread keeps the w rows i-1, i, i+1 of its column in registers and takes the j-1 / j+1
 // neighbours by plain loads.
+// SH: the screened problem (ProblemSpec::sigma != 0): A w + sigma w in the residual, D + sigma in the
+// (z0, r0) partial, in every mode; sigma is InitData's last member, and the launchers pick SH from it.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double resid(double B, double Aw) {
   PMX_NO_CONTRACT
   return B - Aw;
 }
 
-template <typename T, int BLOCK, int MODE>
+template <typename T, int BLOCK, int MODE, bool SH = false>
 __global__ void __launch_bounds__(BLOCK)
 k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T> H,
        double* __restrict__ partials, int TI, int tiles_j, InitData<T> X) {
@@ -108,7 +110,9 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
       if constexpr (MODE == kInitMeasure) {
         const double wp = gi + 1 >= G.M ? 0.0 : wl(c + P);
         const double wjm = djm ? 0.0 : wl(c - 1), wjp = djp ? 0.0 : wl(c + 1);
-        const double e = resid(Bq, apply_a<true>(wc, wm, wp, wjm, wjp, a0, a1, b0, b1, G));
+        double Aw = apply_a<true>(wc, wm, wp, wjm, wjp, a0, a1, b0, b1, G);
+        if constexpr (SH) Aw = __builtin_fma(X.sigma, wc, Aw);  // as apply_a_sh
+        const double e = resid(Bq, Aw);
         acc = __builtin_fma(e, e, acc);
         wm = wc;
         wc = wp;
@@ -117,12 +121,15 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
         if (MODE == kInitData && has_w) {
           const double wp = gi + 1 >= G.M ? 0.0 : wl(c + P);
           const double wjm = djm ? 0.0 : wl(c - 1), wjp = djp ? 0.0 : wl(c + 1);
-          rs = static_cast<T>(resid(Bq, apply_a<true>(wc, wm, wp, wjm, wjp, a0, a1, b0, b1, G)));
+          double Aw = apply_a<true>(wc, wm, wp, wjm, wjp, a0, a1, b0, b1, G);
+          if constexpr (SH) Aw = __builtin_fma(X.sigma, wc, Aw);  // as apply_a_sh
+          rs = static_cast<T>(resid(Bq, Aw));
           wm = wc;
           wc = wp;
         }
         const double rq = static_cast<double>(rs);
-        const double D = diag<true>(a0, a1, b0, b1, G);
+        double D = diag<true>(a0, a1, b0, b1, G);
+        if constexpr (SH) D = add_sigma(D, X.sigma);
         const double z = (D != 0.0) ? rq / D : 0.0;
         acc += z * rq;
         r[c] = rs;
@@ -254,10 +261,18 @@ __global__ void k_local_allreduce(double* const* bufs, int nranks, int nq) {
 
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
-                 double* partials, const TileCfg& tc, hipStream_t s) {
-  PMX_BLOCK_DISPATCH(tc.block,
-      hipLaunchKernelGGL((k_init<T, B, kInitPlain>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
-                         partials, tc.rows, tc.tiles_j, InitData<T>{}));
+                 double* partials, const TileCfg& tc, hipStream_t s, double sigma) {
+  if (sigma != 0.0) {
+    InitData<T> X;
+    X.sigma = sigma;
+    PMX_BLOCK_DISPATCH(tc.block,
+        hipLaunchKernelGGL((k_init<T, B, kInitPlain, true>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
+                           partials, tc.rows, tc.tiles_j, X));
+  } else {
+    PMX_BLOCK_DISPATCH(tc.block,
+        hipLaunchKernelGGL((k_init<T, B, kInitPlain>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
+                           partials, tc.rows, tc.tiles_j, InitData<T>{}));
+  }
   HIP_CHECK(hipGetLastError());
 }
 
@@ -265,8 +280,15 @@ template <typename T>
 void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
                       const TileCfg& tc, const InitData<T>& X, bool measure, hipStream_t s) {
   PMX_CHECK(tc.block == 256, "the data init runs the init tiling (256 columns per tile)");
-  if (measure)
+  const bool sh = X.sigma != 0.0;
+  if (measure && sh)
+    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, true>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+                       partials, tc.rows, tc.tiles_j, X);
+  else if (measure)
     hipLaunchKernelGGL((k_init<T, 256, kInitMeasure>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+                       partials, tc.rows, tc.tiles_j, X);
+  else if (sh)
+    hipLaunchKernelGGL((k_init<T, 256, kInitData, true>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
                        partials, tc.rows, tc.tiles_j, X);
   else
     hipLaunchKernelGGL((k_init<T, 256, kInitData>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
@@ -304,7 +326,7 @@ void launch_local_allreduce(double* const* bufs, int nranks, int nq, hipStream_t
 
 #define PMX_INST(T)                                                                              \
   template void launch_init<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>, double*,  \
-                               const TileCfg&, hipStream_t);                                     \
+                               const TileCfg&, hipStream_t, double);                             \
   template void launch_init_data<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>,       \
                                     double*, const TileCfg&, const InitData<T>&, bool,           \
                                     hipStream_t);                                                 \

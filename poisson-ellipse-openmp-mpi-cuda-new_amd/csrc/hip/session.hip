@@ -8,6 +8,7 @@
 #include <fstream>
 #include <mutex>
 #include <set>
+#include <stdexcept>
 #include <thread>
 
 #include "pmx/common.hpp"
@@ -41,6 +42,7 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
   // a multi-process RCCL run tracks device progress for its hang watchdog (GpuOptions::progress)
   if ((cfg_.comm == CommKind::kRccl || cfg_.comm == CommKind::kIpc) && cfg_.world > 1) pre.progress = 1;
   GpuOptions base = resolve_options(pre);
+  apply_sigma_rules(cfg_.spec, pg_, base);  // sigma != 0: pcg1 on the row march, or std::invalid_argument
   if (base.algo == -1) {
     HIP_CHECK(hipSetDevice(cfg_.devices[0]));
     size_t free_b = 0, total_b = 0;
@@ -187,6 +189,9 @@ bool Session::direct_rows() const {
 void Session::progress(int i, long long out[3]) const { solvers_.at(size_t(i))->progress(out); }
 
 ErrorStats Session::error_norms() {
+  if (cfg_.spec.sigma != 0.0)
+    throw std::invalid_argument("error_norms: the closed-form solution holds for sigma = 0 only; compare the "
+                                "solution with your own (PoissonEllipse.error_norms(w, exact=u))");
   synchronize();
   ErrorStats t;
   t.max_w = -HUGE_VAL;
@@ -419,11 +424,18 @@ std::vector<double> Session::gather_local_w() {
   return g;
 }
 
+void Session::require_no_sigma(const char* what) const {
+  if (cfg_.spec.sigma != 0.0)
+    throw std::invalid_argument(std::string(what) + ": checkpoint files do not record sigma (format v7); "
+                                "sessions with sigma != 0 cannot be checkpointed");
+}
+
 std::string Session::checkpoint_file(const std::string& path, int rank) const {
   return cfg_.world == 1 ? path : path + ".rank" + std::to_string(rank);
 }
 
 void Session::save_checkpoint(const std::string& path) {
+  require_no_sigma("save_checkpoint");
   synchronize();
   for (size_t i = 0; i < solvers_.size(); ++i) {
     const std::string f = checkpoint_file(path, solvers_[i]->sd().rank);
@@ -438,6 +450,7 @@ void Session::save_checkpoint(const std::string& path) {
 }
 
 void Session::load_checkpoint(const std::string& path) {
+  require_no_sigma("load_checkpoint");
   synchronize();
   for (size_t i = 0; i < solvers_.size(); ++i) {
     const std::string f = checkpoint_file(path, solvers_[i]->sd().rank);
@@ -449,6 +462,7 @@ void Session::load_checkpoint(const std::string& path) {
 
 RunStats Session::solve_checkpointed(const std::string& save_path, int64_t every,
                                      const std::string& resume_path, int poll_batches) {
+  require_no_sigma("solve_checkpointed");
   const bool resume = !resume_path.empty();
   if (resume) load_checkpoint(resume_path);
   return solve_impl(poll_batches, !resume, every, save_path);
@@ -458,6 +472,7 @@ std::vector<std::vector<CommEvent>> record_comm_sequence(const ProblemSpec& spec
                                                          const GpuOptions& opt, int64_t iters) {
   const ProcGrid pg = make_process_grid(world, spec.M, spec.N, split);
   GpuOptions o = resolve_options(opt);
+  apply_sigma_rules(spec, pg, o);
   if (o.algo == -1) o.algo = choose_algo(spec, pg, o, 0.0, world, true);
   std::vector<std::unique_ptr<GpuSubdomainSolver>> solvers;
   std::vector<std::vector<CommEvent>> logs(static_cast<size_t>(world));

@@ -47,7 +47,9 @@ struct DevGeom {
   int ref_ellipse;
   double h1, h2, eps, inv_eps, h1h2;
   double cx, cy;  // 1/h1^2, 1/h2^2
-  double dinv_in, dinv_out;  // 1/D for all-inside / all-outside stencils (fast mode)
+  // 1/D for all-inside / all-outside stencils (fast mode); D + sigma for the screened problem, whose
+  // sigma itself travels to the kernels built for it in their own last argument (Pcg1Part, InitData)
+  double dinv_in, dinv_out;
   double ax, by, F;
 };
 

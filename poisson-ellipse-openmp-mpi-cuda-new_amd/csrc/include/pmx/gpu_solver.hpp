@@ -186,6 +186,11 @@ bool choose_single_pass(const ProblemSpec& spec, const ProcGrid& grid, const Gpu
 // whose 7 fields fit into the device (`device_total_bytes` > 0; else no size test), otherwise
 // choose_single_pass.  A pure function of global data: every rank makes the same choice.
 constexpr int64_t kCaAutoPoints = 6000000;
+// The screened problem (ProblemSpec::sigma != 0) runs pcg1 on the row march only.  Turns auto choices
+// into that (algo 1 at any grid size, block tiles off) and throws std::invalid_argument, naming the
+// option, for an explicit s-step / pcg2 / exact arithmetic / block tiles.  No-op with sigma == 0.
+// Called before anything is allocated (Session, GpuSubdomainSolver).
+void apply_sigma_rules(const ProblemSpec& spec, const ProcGrid& grid, GpuOptions& resolved);
 int choose_algo(const ProblemSpec& spec, const ProcGrid& grid, const GpuOptions& resolved, double device_total_bytes,
                 int subdomains_per_device, bool direct_rows = true);
 

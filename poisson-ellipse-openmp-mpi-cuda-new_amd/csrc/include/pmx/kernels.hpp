@@ -84,7 +84,7 @@ enum AblBits : int {
 
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
-                 double* partials, const TileCfg& tc, hipStream_t s);
+                 double* partials, const TileCfg& tc, hipStream_t s, double sigma = 0.0);
 
 // k_init with data (GpuSubdomainSolver::set_init_data / residual_norm), on launch_init's tiling.
 //   data init (measure = false): r holds f on the owned nodes (has_f; else the constant G.F), w holds
@@ -103,6 +103,8 @@ struct InitData {
   const T* pb = nullptr;
   double ca = 0.0, cb = 0.0;
   int npend = 0;
+  // screened problem (ProblemSpec::sigma): != 0 launches the kernels built for A + sigma I, D + sigma
+  double sigma = 0.0;
 };
 template <typename T>
 void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
@@ -142,7 +144,7 @@ size_t pcg1_order_slots(const TileCfg& tc);  // d_order capacity pcg1_build_orde
 template <typename T>
 void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0, T* p1,
                  double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part = 0,
-                 bool wsweep = false);
+                 bool wsweep = false, double sigma = 0.0);  // sigma: ProblemSpec::sigma (!= 0: the SH sweeps)
 
 // pcg1 sweep with block tiles (pcg1_block.hip): one workgroup per tc.rows x 124 tile, the three
 // pipeline stages row-parallel; undecomposed fp64 grids; partial sums per tile as k_pcg1.  With a ticket the sweep also finishes the reduction (red_c =

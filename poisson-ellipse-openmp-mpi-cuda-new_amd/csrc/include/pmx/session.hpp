@@ -101,6 +101,8 @@ class Session {
   void save_checkpoint(const std::string& path);
   void load_checkpoint(const std::string& path);
   std::string checkpoint_file(const std::string& path, int rank) const;
+  // checkpoints do not record ProblemSpec::sigma: std::invalid_argument when it is not 0
+  void require_no_sigma(const char* what) const;
   RunStats profile(int64_t n);  // threaded: every bucket is the MAX over the owned ranks
   PcgState state(int i = 0);
   bool threaded() const { return threaded_; }  // one host thread per owned rank

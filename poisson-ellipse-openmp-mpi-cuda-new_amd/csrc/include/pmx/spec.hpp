@@ -7,6 +7,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <string>
 
@@ -45,6 +46,10 @@ struct ProblemSpec {
   // absolute and (A p, p) shrinks like h^3 for this problem, so grids beyond ~100000^2 trip it at
   // the first iteration; lower it (e.g. 0) there.
   double breakdown_tol = 1e-15;
+  // Screened problem (-div(k grad u) + sigma u = f): the shift added to the operator and to its
+  // diagonal on every interior node of the box.  0 (the reference's problem) changes nothing.  An
+  // extension without a counterpart in the reference (docs/PARITY.md).
+  double sigma = 0.0;
 
   int64_t effective_max_iter() const {
     return max_iter >= 0 ? max_iter : int64_t(M - 1) * int64_t(N - 1);
@@ -60,6 +65,7 @@ struct ProblemSpec {
     PMX_CHECK(ax > 0 && by > 0, "ellipse semi-axes must be positive");
     PMX_CHECK(delta > 0, "delta must be positive");
     PMX_CHECK(breakdown_tol >= 0, "breakdown tolerance must be >= 0");
+    PMX_CHECK(std::isfinite(sigma) && sigma >= 0, "sigma must be finite and >= 0, got " << sigma);
   }
 };
 

@@ -31,12 +31,19 @@ class PoissonEllipse:
     max_iter: Optional[int] = None   # None -> (M-1)(N-1)  (stage0/Withoutopenmp1.cpp:182)
     norm: str = "weighted"   # "weighted" (stages 1-4) | "unweighted" (stage 0)
     breakdown_tol: float = 1e-15     # CG guard on (Ap,p) (stage0/Withoutopenmp1.cpp:130); see spec.hpp
+    sigma: float = 0.0       # screened problem (-Δ + σ) u = f, σ >= 0 constant; 0 = the reference's problem
 
     def __post_init__(self):
         if self.norm not in ("weighted", "unweighted"):
             raise ValueError(f"norm must be weighted|unweighted, got {self.norm!r}")
         if self.M < 2 or self.N < 2:
             raise ValueError("grid must be at least 2x2 cells")
+        try:
+            self.sigma = float(self.sigma)
+        except (TypeError, ValueError):
+            raise ValueError(f"sigma must be a finite number >= 0, got {self.sigma!r}") from None
+        if not math.isfinite(self.sigma) or self.sigma < 0:
+            raise ValueError(f"sigma must be finite and >= 0, got {self.sigma!r}")
 
     # ---- derived quantities (stage0/Withoutopenmp1.cpp:107-108) ----
     @property
@@ -64,7 +71,7 @@ class PoissonEllipse:
     def to_native(self):
         n = _native()
         s = n.ProblemSpec()
-        for f in ("M", "N", "A1", "B1", "A2", "B2", "ax", "by", "F", "delta", "breakdown_tol"):
+        for f in ("M", "N", "A1", "B1", "A2", "B2", "ax", "by", "F", "delta", "breakdown_tol", "sigma"):
             setattr(s, f, getattr(self, f))
         s.max_iter = -1 if self.max_iter is None else int(self.max_iter)
         s.norm = n.Norm.weighted if self.norm == "weighted" else n.Norm.unweighted
@@ -79,10 +86,17 @@ class PoissonEllipse:
     def exact_solution(self, x, y):
         """u = F (1 - x²/ax² - y²/by²) / (2/ax² + 2/by²) inside D, 0 outside.
 
-        For the reference ellipse this is (1 - x² - 4y²)/10 (итоговый отчёт/Этап_4_1213.pdf p.1)."""
+        For the reference ellipse this is (1 - x² - 4y²)/10 (итоговый отчёт/Этап_4_1213.pdf p.1).
+        It solves the σ = 0 problem only: with sigma != 0 this raises ValueError."""
+        self.require_closed_form("exact_solution")
         q = 1.0 - (x / self.ax) ** 2 - (y / self.by) ** 2
         c = self.F / (2.0 / self.ax ** 2 + 2.0 / self.by ** 2)
         return np.where(q > 0, c * q, 0.0)
+
+    def require_closed_form(self, what: str):
+        if self.sigma != 0.0:
+            raise ValueError(f"{what}: the closed-form solution holds for sigma = 0 only (sigma = {self.sigma}); "
+                             "pass the solution of your problem as exact=")
 
     def inside_mask(self):
         x, y = self.coords()
@@ -94,6 +108,7 @@ class PoissonEllipse:
     def local_error_stats(self, sd: dict, local: np.ndarray) -> dict:
         """Unreduced error statistics of one subdomain's interior block (nx x ny, global nodes
         i_start..i_end x j_start..j_end): the host twin of the device k_error_norms."""
+        self.require_closed_form("local_error_stats")
         x, y = self.coords()
         X, Y = np.meshgrid(x[sd["i_start"]:sd["i_end"] + 1], y[sd["j_start"]:sd["j_end"] + 1], indexing="ij")
         u = self.exact_solution(X, Y)

@@ -50,7 +50,10 @@ def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
     place of the constant F (the solver applies the ellipse mask: values outside D and on the box
     boundary are ignored) and an initial iterate in place of w = 0.  The hip backend also takes float64
     tensors on its device for both and returns one with keep_solution="device" (solve_hip); every other
-    backend rejects device tensors."""
+    backend rejects device tensors.
+
+    problem.sigma != 0 (the screened problem (-Δ + σ) u = f): every backend solves it; hip runs pcg1 on the
+    row march at any grid size and raises ValueError for algo="ca" / "pcg2", exact=True and block_tiles=1."""
     if backend in ("cpu", "serial"):
         return solve_cpu(problem, threads=1, **kw)
     if backend in ("omp", "openmp"):

@@ -84,6 +84,8 @@ class TorchSStepPCG:
         self.gram = gram
         if s < 1:
             raise ValueError("s must be >= 1")
+        if getattr(problem, "sigma", 0.0) != 0.0:
+            raise ValueError("the s-step PCG is not built for sigma != 0")
         self.p = problem
         self.s = s
         self.device = torch.device(device)

@@ -71,10 +71,10 @@ class TorchPCG:
                 edge.zero_()
         if w0 is not None:
             wl = self._local(w0)  # the ring comes from the global array: no exchange
-            self.r[1:-1, 1:-1] -= R.apply_A(wl, self.a, self.b, h1, h2)
+            self.r[1:-1, 1:-1] -= R.apply_A(wl, self.a, self.b, h1, h2, P.sigma)
             self.w[1:-1, 1:-1] = wl[1:-1, 1:-1]
         self.pv = torch.zeros_like(self.w)
-        z = R.precond(self.r, self.a, self.b, h1, h2)
+        z = R.precond(self.r, self.a, self.b, h1, h2, P.sigma)
         self.pv[1:-1, 1:-1] = z
         self.zr_old = self._allsum(R.dot(z, self.r[1:-1, 1:-1], h1, h2))
         self.k = 1
@@ -96,7 +96,7 @@ class TorchPCG:
             k = self.k
             self.iters = k
             self._exchange(p)
-            Ap = R.apply_A(p, a, b, h1, h2)
+            Ap = R.apply_A(p, a, b, h1, h2, P.sigma)
             denom = self._allsum(R.dot(Ap, p[1:-1, 1:-1], h1, h2))
             tol = P.breakdown_tol
             if (abs(denom) < tol) if weighted else (denom < tol):
@@ -106,7 +106,7 @@ class TorchPCG:
             w_old = w[1:-1, 1:-1].clone()
             w[1:-1, 1:-1] += alpha * p[1:-1, 1:-1]
             r[1:-1, 1:-1] -= alpha * Ap
-            z = R.precond(r, a, b, h1, h2)
+            z = R.precond(r, a, b, h1, h2, P.sigma)
             zr_new = self._allsum(R.dot(z, r[1:-1, 1:-1], h1, h2))
             dw = w[1:-1, 1:-1] - w_old
             dsum = self._allsum((dw * dw).sum(dtype=torch.float64))

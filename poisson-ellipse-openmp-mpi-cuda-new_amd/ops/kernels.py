@@ -13,6 +13,9 @@ from ..utils.native import load as _native
 
 class DeviceOps:
     def __init__(self, problem, Px: int = 1, Py: int = 1, rank: int = 0, device: int = 0):
+        if getattr(problem, "sigma", 0.0) != 0.0:
+            raise ValueError("DeviceOps evaluates -div(k grad u) alone: not built for sigma != 0 (use a native "
+                             "session: solve(problem, 'hip') / make_session)")
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceOps needs a GPU (HIP device)")
         self.problem = problem

@@ -76,21 +76,23 @@ def assemble(problem, sd, device="cpu", dtype=torch.float64):
     return a.to(dtype), b.to(dtype), B.to(dtype)
 
 
-def apply_A(p, a, b, h1, h2):
-    """(A p) on the interior; p must carry valid ghosts.  Returns (nx, ny)."""
+def apply_A(p, a, b, h1, h2, sigma=0.0):
+    """(A p) on the interior, plus sigma p for the screened problem; p must carry valid ghosts.
+    Returns (nx, ny)."""
     c = p[1:-1, 1:-1]
     ax = -1.0 / h1 * (a[2:, 1:-1] * (p[2:, 1:-1] - c) / h1 - a[1:-1, 1:-1] * (c - p[:-2, 1:-1]) / h1)
     ay = -1.0 / h2 * (b[1:-1, 2:] * (p[1:-1, 2:] - c) / h2 - b[1:-1, 1:-1] * (c - p[1:-1, :-2]) / h2)
-    return ax + ay
+    return (ax + ay) + sigma * c if sigma != 0.0 else ax + ay
 
 
-def diag(a, b, h1, h2):
-    return (a[2:, 1:-1] + a[1:-1, 1:-1]) / (h1 * h1) + (b[1:-1, 2:] + b[1:-1, 1:-1]) / (h2 * h2)
+def diag(a, b, h1, h2, sigma=0.0):
+    D = (a[2:, 1:-1] + a[1:-1, 1:-1]) / (h1 * h1) + (b[1:-1, 2:] + b[1:-1, 1:-1]) / (h2 * h2)
+    return D + sigma if sigma != 0.0 else D
 
 
-def precond(r, a, b, h1, h2):
-    """z = D^-1 r on the interior.  Returns (nx, ny)."""
-    D = diag(a, b, h1, h2)
+def precond(r, a, b, h1, h2, sigma=0.0):
+    """z = D^-1 r on the interior (D includes sigma).  Returns (nx, ny)."""
+    D = diag(a, b, h1, h2, sigma)
     return torch.where(D != 0, r[1:-1, 1:-1] / D, torch.zeros_like(D))
 
 
