@@ -5,7 +5,7 @@
 // (ellipse x^2+4y^2<1, delta=1e-6, max_iter=(M-1)(N-1), weighted norm).  The superset:
 //
 //   pmx [M N] [--ax 1.0 --by 0.5] [--box -1,1,-0.6,0.6] [--f 1.0] [--delta 1e-6] [--max-iter K]
-//       [--breakdown-tol 1e-15] [--sigma 0]
+//       [--breakdown-tol 1e-15] [--sigma 0] [--stop step|residual --rtol 1e-8 --atol 0]
 //       [--backend cpu|omp|hip] [--threads T] [--ranks P] [--gpus G] [--comm self|local|rccl]
 //       [--split reference|auto|rows|cols] [--dtype fp64|fp32|mixed] [--norm weighted|unweighted]
 //       [--exact] [--graph-batch 32] [--tile-rows 0] [--kernel wave] [--vec 2] [--waves 4]
@@ -51,7 +51,7 @@ struct Cli {
 [[noreturn]] void usage(const char* msg) {
   if (msg) std::cerr << "pmx: " << msg << "\n";
   std::cerr << "usage: pmx [M N] [--ax A] [--by B] [--box a1,b1,a2,b2] [--f F] [--delta D] [--max-iter K]\n"
-               "           [--breakdown-tol T] [--sigma S]\n"
+               "           [--breakdown-tol T] [--sigma S] [--stop step|residual] [--rtol R] [--atol A]\n"
                "           [--backend cpu|omp|hip] [--threads T] [--ranks P] [--gpus G]\n"
                "           [--comm self|local|rccl] [--split reference|auto|rows|cols]\n"
                "           [--dtype fp64|fp32|mixed] [--norm weighted|unweighted] [--exact]\n"
@@ -91,6 +91,13 @@ Cli parse(int argc, char** argv) {
     else if (a == "--breakdown-tol") c.spec.breakdown_tol = std::atof(val().c_str());
     else if (a == "--max-iter") c.spec.max_iter = std::atoll(val().c_str());
     else if (a == "--sigma") c.spec.sigma = std::atof(val().c_str());  // (-Δ + sigma) u = f, sigma >= 0
+    else if (a == "--stop") {
+      const std::string v = val();
+      if (v != "step" && v != "residual") usage("--stop step|residual");
+      c.spec.stop = v == "residual" ? StopRule::kResidual : StopRule::kStep;
+    }
+    else if (a == "--rtol") c.spec.rtol = std::atof(val().c_str());
+    else if (a == "--atol") c.spec.atol = std::atof(val().c_str());
     else if (a == "--box") {
       const std::string v = val();
       if (std::sscanf(v.c_str(), "%lf,%lf,%lf,%lf", &c.spec.A1, &c.spec.B1, &c.spec.A2, &c.spec.B2) != 4)
@@ -217,7 +224,7 @@ int run_cpu(Cli& c, double t_prog, bool header = true, bool footer = true) {
   const int threads = c.backend == "cpu" ? 1 : c.threads;
   SolveResult r = c.ranks > 1 ? cpu_solve_decomposed(s, c.ranks, parse_split(c.split), threads, true)
                               : cpu_solve(s, threads, true);
-  if (r.status == Status::kConverged) print_converged(r.iters, s.delta, stage0 || c.banner == "stage1");
+  if (r.status == Status::kConverged) print_converged(r.iters, s, stage0 || c.banner == "stage1");
   if (c.banner == "stage1") {
     std::cout << "Threads = " << std::setw(2) << threads << " | Time = " << std::fixed << std::setprecision(3)
               << r.seconds << " s\n";
@@ -235,7 +242,11 @@ int run_cpu(Cli& c, double t_prog, bool header = true, bool footer = true) {
         .kv("mlups", double(s.M - 1) * (s.N - 1) * r.iters / r.seconds / 1e6);
     // the closed-form solution the errors compare with holds for sigma = 0 only
     if (s.sigma == 0.0) j.kv("l2_error", e.l2).kv("max_error", e.max_err);
-    j.kv("max_w", e.max_w).kv("sigma", s.sigma).kv("total_seconds", now() - t_prog);
+    j.kv("max_w", e.max_w).kv("sigma", s.sigma);
+    if (s.stop == StopRule::kResidual)
+      j.ks("stop", "residual").kv("rtol", s.rtol).kv("atol", s.atol).kv("residual", r.residual)
+          .kv("residual_ref", r.residual_ref);
+    j.kv("total_seconds", now() - t_prog);
     std::cout << j.str() << std::endl;
   }
   return 0;
@@ -320,7 +331,7 @@ int run_hip(Cli& c, double t_prog) {
   }
   if (!c.checkpoint.empty()) sess.save_checkpoint(c.checkpoint);  // final state
   const double t_after = now();
-  if (st.status == Status::kConverged) print_converged(st.iters, s.delta, false);
+  if (st.status == Status::kConverged) print_converged(st.iters, s, false);
   std::vector<double> w;  // gathered before profiling, which restarts the solver
   if (!c.dump.empty() || c.json) w = sess.gather_local_w();
   RunStats ph;
@@ -355,8 +366,11 @@ int run_hip(Cli& c, double t_prog) {
         .kv("mlups", double(s.M - 1) * (s.N - 1) * st.iters / st.solve_seconds / 1e6)
         .kv("us_per_iter", st.solve_seconds / std::max<int64_t>(1, st.iters) * 1e6);
     if (s.sigma == 0.0) j.kv("l2_error", e.l2).kv("max_error", e.max_err);  // (closed form: sigma = 0 only)
-    j.kv("max_w", e.max_w).kv("sigma", s.sigma)
-        .kv("device_bytes", sess.device_bytes()).kv("total_seconds", now() - t_prog);
+    j.kv("max_w", e.max_w).kv("sigma", s.sigma);
+    if (s.stop == StopRule::kResidual)
+      j.ks("stop", "residual").kv("rtol", s.rtol).kv("atol", s.atol).kv("residual", st.residual)
+          .kv("residual_ref", st.residual_ref);
+    j.kv("device_bytes", sess.device_bytes()).kv("total_seconds", now() - t_prog);
     if (c.profile > 0)
       j.kv("profiled_iters", c.profile).kv("phase_kernel_a_s", ph.t_kernel_a)
           .kv("phase_kernel_b_s", ph.t_kernel_b).kv("phase_reduce_s", ph.t_reduce)

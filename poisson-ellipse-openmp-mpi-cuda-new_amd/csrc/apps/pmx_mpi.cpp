@@ -49,6 +49,17 @@ int main(int argc, char** argv) {
       const std::string v = val();
       split = v == "auto" ? Split::kAuto : v == "rows" ? Split::kRows : v == "cols" ? Split::kCols : Split::kReference;
     } else if (a == "--delta") spec.delta = std::atof(val().c_str());
+    else if (a == "--stop") {
+      const std::string v = val();
+      if (v != "step" && v != "residual") {
+        if (rank == 0) std::cerr << "pmx_mpi: --stop step|residual, got '" << v << "'\n";
+        MPI_Finalize();
+        return 2;
+      }
+      spec.stop = v == "residual" ? StopRule::kResidual : StopRule::kStep;
+    }
+    else if (a == "--rtol") spec.rtol = std::atof(val().c_str());
+    else if (a == "--atol") spec.atol = std::atof(val().c_str());
     else if (a == "--max-iter") spec.max_iter = std::atoll(val().c_str());
     else if (a == "--breakdown-tol") spec.breakdown_tol = std::atof(val().c_str());
     else pos.push_back(a);
@@ -116,7 +127,7 @@ int main(int argc, char** argv) {
       MPI_Reduce(w.data(), rank == 0 ? g.data() : nullptr, int(w.size()), MPI_DOUBLE, MPI_SUM, 0, MPI_COMM_WORLD);
     }
     if (rank == 0) {
-      if (r.status == Status::kConverged) print_converged(r.iters, spec.delta, false);
+      if (r.status == Status::kConverged) print_converged(r.iters, spec, false);
       std::cout << "M=" << spec.M << ", N=" << spec.N << " | Iter=" << r.iters << " | Time=" << std::fixed
                 << std::setprecision(6) << elapsed << " s\n";
       if (phases)

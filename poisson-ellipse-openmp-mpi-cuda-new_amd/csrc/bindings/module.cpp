@@ -143,6 +143,13 @@ void refuse_sigma(const ProblemSpec& s, const char* what) {
                           "Session (solve(..., \"hip\"), make_session, DistGpuPCG comm=\"native\")");
 }
 
+// ... and their host loop owns the reference's stop test alone.
+void refuse_stop(const ProblemSpec& s, const char* what) {
+  if (s.stop != StopRule::kStep)
+    throw py::value_error(std::string(what) + " is not built for stop=\"residual\": use a native Session "
+                          "(solve(..., \"hip\"), make_session, DistGpuPCG comm=\"native\")");
+}
+
 py::dict sd_dict(const Subdomain& s) {
   py::dict d;
   d["M"] = s.M; d["N"] = s.N; d["Px"] = s.grid.Px; d["Py"] = s.grid.Py;
@@ -160,6 +167,10 @@ py::dict result_dict(const SolveResult& r, const ProblemSpec& s, bool with_w) {
   d["status"] = std::string(status_name(r.status));
   d["diff"] = r.last_diff;
   d["seconds"] = r.seconds;
+  if (s.stop == StopRule::kResidual) {
+    d["residual"] = r.residual;
+    d["residual_ref"] = r.residual_ref;
+  }
   if (with_w && !r.w.empty()) d["w"] = to_numpy(r.w, {s.M + 1, s.N + 1});
   return d;
 }
@@ -182,6 +193,11 @@ py::dict state_dict(const PcgState& st) {
   d["alpha1"] = py::make_tuple(st.alpha1[0], st.alpha1[1], st.alpha1[2], st.alpha1[3]);
   d["beta1"] = py::make_tuple(st.beta1[0], st.beta1[1], st.beta1[2], st.beta1[3]);
   d["halo_k"] = st.halo_k;
+  if (st.stop == int(StopRule::kResidual)) {  // sqrt(rho) of the last tested iterate, sqrt(rho_B) (spec.hpp)
+    d["stop"] = std::string(stop_rule_name(StopRule(st.stop)));
+    d["residual"] = std::sqrt(st.stop_rho);
+    d["residual_ref"] = std::sqrt(st.rho_b);
+  }
   return d;
 }
 
@@ -202,6 +218,10 @@ py::dict stats_dict(const RunStats& r) {
   d["solve_seconds"] = r.solve_seconds;
   d["launched"] = r.launched;
   d["nan"] = r.nan;
+  if (r.residual_rule) {
+    d["residual"] = r.residual;
+    d["residual_ref"] = r.residual_ref;
+  }
   d["t_kernel_a"] = r.t_kernel_a;
   d["t_kernel_b"] = r.t_kernel_b;
   d["t_comm"] = r.t_comm;
@@ -341,6 +361,8 @@ PYBIND11_MODULE(_pmx, m) {
   py::register_exception<pmx::Error>(m, "PmxError", PyExc_RuntimeError);
 
   py::enum_<Norm>(m, "Norm", py::module_local()).value("weighted", Norm::kWeighted).value("unweighted", Norm::kUnweighted);
+  py::enum_<StopRule>(m, "StopRule", py::module_local()).value("step", StopRule::kStep).value("residual", StopRule::kResidual);
+  m.attr("state_bytes") = sizeof(PcgState);
   py::enum_<Split>(m, "Split", py::module_local())
       .value("reference", Split::kReference).value("auto", Split::kAuto)
       .value("rows", Split::kRows).value("cols", Split::kCols);
@@ -354,6 +376,8 @@ PYBIND11_MODULE(_pmx, m) {
       .def_readwrite("F", &ProblemSpec::F).def_readwrite("delta", &ProblemSpec::delta)
       .def_readwrite("breakdown_tol", &ProblemSpec::breakdown_tol)
       .def_readwrite("sigma", &ProblemSpec::sigma)
+      .def_readwrite("stop", &ProblemSpec::stop).def_readwrite("rtol", &ProblemSpec::rtol)
+      .def_readwrite("atol", &ProblemSpec::atol)
       .def_readwrite("max_iter", &ProblemSpec::max_iter).def_readwrite("norm", &ProblemSpec::norm)
       .def("effective_max_iter", &ProblemSpec::effective_max_iter)
       .def("validate", &ProblemSpec::validate);
@@ -456,6 +480,7 @@ PYBIND11_MODULE(_pmx, m) {
   m.def("comm_layout", [](const ProblemSpec& s, int Px, int Py, int rank, const std::string& dtype,
                           const std::string& kernel, bool exact, int device, int algo, int sharing) {
           refuse_sigma(s, "comm_layout (the Python-orchestrated solver)");
+          refuse_stop(s, "comm_layout (the Python-orchestrated solver)");
           GpuOptions o = make_options(device, kernel, 256, 0, 4, 0, dtype, exact, 0, false);
           o.algo = algo;
           o = resolve_options(o);
@@ -535,6 +560,7 @@ PYBIND11_MODULE(_pmx, m) {
                        const std::string& dtype, bool exact, uintptr_t arena, bool check, int vec_b,
                        int waves_b, int tile_rows_b, bool b_ring, int algo) {
              refuse_sigma(s, "SubdomainSolver (the Python-orchestrated solver)");
+             refuse_stop(s, "SubdomainSolver (the Python-orchestrated solver)");
              const Subdomain sd = decompose_2d(s.M, s.N, ProcGrid{Px, Py}, rank);
              return std::make_unique<GpuSubdomainSolver>(
                  s, sd, make_options(device, kernel, block, vec, waves, tile_rows, dtype, exact, 0, check,

@@ -111,7 +111,13 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
       }
   };
 
+  const bool residual_rule = spec.stop == StopRule::kResidual;
+  double rho_b = 0.0;
   if (w0) {  // r^0 = B - A w0
+    if (residual_rule) {  // rho_B = (D^-1 B, B) while r still holds B
+      mat_D();
+      rho_b = dot(z, r);
+    }
     p = w;
     mat_A();
     for (int i = 1; i <= M - 1; ++i)
@@ -122,7 +128,12 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
   double zr_old = dot(z, r);
   SolveResult res;
   const int64_t max_iter = spec.effective_max_iter();
-  for (int64_t k = 1; k <= max_iter; ++k) {
+  if (!w0) rho_b = zr_old;
+  const double thr = residual_rule ? spec.residual_threshold(rho_b) : 0.0;
+  // the residual rule tests rho_0 too: a start that is already good enough ends with 0 iterations
+  const bool met0 = residual_rule && ProblemSpec::residual_met(zr_old, thr);
+  if (met0) res.status = Status::kConverged;
+  for (int64_t k = 1; k <= max_iter && !met0; ++k) {
     res.iters = k;
     mat_A();
     const double denom = dot(Ap, p);
@@ -142,7 +153,11 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
     mat_D();
     const double zr_new = dot(z, r);
     res.last_diff = norm_of(dsum, spec, g);
-    if (res.last_diff < spec.delta) { res.status = Status::kConverged; break; }
+    if (residual_rule ? ProblemSpec::residual_met(zr_new, thr) : res.last_diff < spec.delta) {
+      zr_old = zr_new;
+      res.status = Status::kConverged;
+      break;
+    }
     const double beta = zr_new / zr_old;
     zr_old = zr_new;
 #pragma omp parallel for collapse(2) num_threads(nt) if (nt > 1)
@@ -153,6 +168,10 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
       }
   }
   if (res.status == Status::kRunning) res.status = Status::kMaxIter;
+  if (residual_rule) {
+    res.residual = std::sqrt(zr_old);
+    res.residual_ref = std::sqrt(rho_b);
+  }
   res.seconds = timer.seconds();
   if (keep_solution) {
     res.w.assign(size_t(M + 1) * (N + 1), 0.0);
@@ -272,6 +291,22 @@ double CpuSubdomain::precond_dot() {
   return sum * h1 * h2;
 }
 
+double CpuSubdomain::rhs_dot() const {
+  const int nx = sd_.nx, ny = sd_.ny, P = ny + 2, nt = threads_;
+  const double h1 = g_.h1, h2 = g_.h2, sigma = spec_.sigma;
+  const double* a = a_.data(); const double* b = b_.data(); const double* B = B_.data();
+  double sum = 0.0;
+#pragma omp parallel for collapse(2) reduction(+ : sum) num_threads(nt) if (nt > 1)
+  for (int li = 1; li <= nx; ++li)
+    for (int lj = 1; lj <= ny; ++lj) {
+      const size_t c = size_t(li) * P + lj;
+      const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + sigma;
+      const double z = (D != 0.0) ? B[c] / D : 0.0;
+      sum += z * B[c];
+    }
+  return sum * h1 * h2;
+}
+
 void CpuSubdomain::update_p(double beta) {
   const int nx = sd_.nx, ny = sd_.ny, P = ny + 2, nt = threads_;
   double* p = p_.data(); const double* z = z_.data();
@@ -333,7 +368,14 @@ SolveResult cpu_pcg_loop(const ProblemSpec& spec, std::vector<CpuSubdomain*>& lo
   double zr_old = local_sum([](CpuSubdomain& d) { return d.init(); });
   SolveResult res;
   const int64_t max_iter = spec.effective_max_iter();
-  for (int64_t k = 1; k <= max_iter; ++k) {
+  const bool residual_rule = spec.stop == StopRule::kResidual;
+  // every rank holds w0 or none does (one global array), so the extra reduction is collective
+  const bool warm = !local.empty() && local[0]->has_w0();
+  const double rho_b = residual_rule && warm ? local_sum([](CpuSubdomain& d) { return d.rhs_dot(); }) : zr_old;
+  const double thr = residual_rule ? spec.residual_threshold(rho_b) : 0.0;
+  const bool met0 = residual_rule && ProblemSpec::residual_met(zr_old, thr);
+  if (met0) res.status = Status::kConverged;
+  for (int64_t k = 1; k <= max_iter && !met0; ++k) {
     res.iters = k;
     for (auto* d : local) coll.exchange_p_halos(*d);
     const double denom = local_sum([](CpuSubdomain& d) { return d.matvec_dot(); });
@@ -343,12 +385,20 @@ SolveResult cpu_pcg_loop(const ProblemSpec& spec, std::vector<CpuSubdomain*>& lo
     for (auto* d : local) { double x; d->update_wr(alpha, &x); dl += x; }
     const double zr_new = local_sum([](CpuSubdomain& d) { return d.precond_dot(); });
     res.last_diff = norm_of(coll.allreduce_sum(dl), spec, g);
-    if (res.last_diff < spec.delta) { res.status = Status::kConverged; break; }
+    if (residual_rule ? ProblemSpec::residual_met(zr_new, thr) : res.last_diff < spec.delta) {
+      zr_old = zr_new;
+      res.status = Status::kConverged;
+      break;
+    }
     const double beta = zr_new / zr_old;
     zr_old = zr_new;
     for (auto* d : local) d->update_p(beta);
   }
   if (res.status == Status::kRunning) res.status = Status::kMaxIter;
+  if (residual_rule) {
+    res.residual = std::sqrt(zr_old);
+    res.residual_ref = std::sqrt(rho_b);
+  }
   res.seconds = timer.seconds();
   return res;
 }

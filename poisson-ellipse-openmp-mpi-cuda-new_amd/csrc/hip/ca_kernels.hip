@@ -986,7 +986,15 @@ __global__ void __launch_bounds__(256) k_ca_init(DevGeom G, DevTables Tb, T* z, 
 // iterations of this block on the coefficient vectors, from the Gram products t (raw sums), in the
 // classic loop's order of tests (max_iter, the |denominator| guard; the stop test follows in the next
 // reduction).  One lane; writes CaState (pass 2's coefficients and mode) and the PcgState outcome.
-template <int S>
+// RES: StopRule::kResidual.  The scalar lane carries g = (r, z) through the block's iterations; the first j
+// whose g meets the threshold (PcgState::stop_thr2, formed by the init's k_stop_init) ends the block's loop,
+// pass 2 applies exactly n = j + 1 iterations (no rewind), and the solve finishes as converged through the
+// deferred after_status / after_iters path once that pass has run; the pending step test only records diff.
+// RES is a template parameter of the three finishing kernels too (the host picks by ProblemSpec::stop): the
+// step rule's kernels are the code, registers and occupancy of every build before the rule.  (In ONE body
+// with a run-time branch the compiler fused the Gram arithmetic differently: a step-rule solve stepped in
+// batches of 32 moved by 1e-13.)
+template <int S, bool RES>
 __device__ void ca_finish(const double* t, const double* u, double h, double wdiff, int nmax, bool check_only,
                           PcgState* St, CaState* C) {
   using Sh = CaShape<S>;
@@ -1000,7 +1008,7 @@ __device__ void ca_finish(const double* t, const double* u, double h, double wdi
     for (int j = 0; j < n; ++j) {
       diff = fabs(C->alpha[j]) * sqrt(u[j] * wdiff);
       const bool bad = !(diff == diff);
-      if (bad || diff < St->delta) {
+      if (bad || (!RES && diff < St->delta)) {
         const long long kk = C->pend_k + j + 1;
         if (j + 1 < n) {  // w went past the stop: back to w_k + Y c_{j+1}
           for (int i = 0; i < NB; ++i) C->coef[2][i] = C->pc[j][i] - C->pc[n - 1][i];
@@ -1105,7 +1113,15 @@ __device__ void ca_finish(const double* t, const double* u, double h, double wdi
     const double beta = gn / g;
     for (int i = 0; i < NB; ++i) a[i] = __builtin_fma(beta, a[i], b[i]);
     g = gn;
+    if constexpr (RES) {
+      if (g <= St->stop_thr2) {  // rho_{k+j+1} meets the threshold
+        C->after_status = int(Status::kConverged);
+        C->after_iters = k + j + 1;
+        break;
+      }
+    }
   }
+  if constexpr (RES) St->stop_rho = g;  // (z, r) of the newest iterate, for the host's report
   if (n == 0) {  // breakdown in the block's first iteration: nothing to apply or to test
     St->iters = C->after_iters;
     St->status = C->after_status;
@@ -1151,7 +1167,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 // ranges (thread-strided, then waves in order) and publish their chunk sums; the last block to arrive
 // (ticket) sums the chunks in block order, one quantity per lane.  check_only: the norms alone (the
 // pending test after a batch's last block).  Hand-off as k_reduce_n (pcg_device.hpp).
-template <int S>
+template <int S, bool RES = false>
 __global__ void __launch_bounds__(256)
 k_ca_reduce(const double* __restrict__ part, int n, int n2, double h, double wdiff, int nmax, int check_only,
             int finish, PcgState* St, CaState* C, double* chunk, long long* progress) {
@@ -1228,7 +1244,7 @@ k_ca_reduce(const double* __restrict__ part, int n, int n2, double h, double wdi
     wave_copy(&sc, C, lane);
     wave_lds_sync();
     if (lane == 0) {
-      ca_finish<S>(tot, tot + Sh::NQ, h, wdiff, nmax, check_only != 0, &sst, &sc);
+      ca_finish<S, RES>(tot, tot + Sh::NQ, h, wdiff, nmax, check_only != 0, &sst, &sc);
       if (progress) __hip_atomic_store(progress, sst.it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       sc.ticket = 0u;  // re-arm for the next launch (every block has arrived; stream order publishes it)
     }
@@ -1246,7 +1262,7 @@ k_ca_reduce(const double* __restrict__ part, int n, int n2, double h, double wdi
 // sum: ~7 of the ~19 us the multi-block reduction takes at 1600x2400), and the last wave stages the
 // solver state in LDS while the others still load partials.  Fixed order: thread-strided sums, wave
 // sums, then the 16 waves in index order.
-template <int S>
+template <int S, bool RES = false>
 __global__ void __launch_bounds__(1024)
 k_ca_reduce1(const double* __restrict__ part, int n, int n2, double h, double wdiff, int nmax, int check_only,
              int finish, PcgState* St, CaState* C, long long* progress) {
@@ -1294,7 +1310,7 @@ k_ca_reduce1(const double* __restrict__ part, int n, int n2, double h, double wd
   wave_lds_sync();
   if (finish) {
     if (lane == 0) {
-      ca_finish<S>(tot, tot + Sh::NQ, h, wdiff, nmax, check_only != 0, &sst, &sc);
+      ca_finish<S, RES>(tot, tot + Sh::NQ, h, wdiff, nmax, check_only != 0, &sst, &sc);
       if (progress) __hip_atomic_store(progress, sst.it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     wave_lds_sync();
@@ -1306,7 +1322,7 @@ k_ca_reduce1(const double* __restrict__ part, int n, int n2, double h, double wd
 }
 
 // Decomposed grids: ca_finish on the all-reduced sums (CaState::red), after the all-reduce.
-template <int S>
+template <int S, bool RES = false>
 __global__ void __launch_bounds__(64)
 k_ca_finish(double h, double wdiff, int nmax, int check_only, PcgState* St, CaState* C, long long* progress) {
   const int lane = int(threadIdx.x);
@@ -1326,7 +1342,7 @@ k_ca_finish(double h, double wdiff, int nmax, int check_only, PcgState* St, CaSt
         bad |= !(t[q] == t[q]) || isinf(t[q]);
       }
       if (bad) sst.nan_flag = 1;
-      ca_finish<S>(t, t + 6 * S, h, wdiff, nmax, check_only != 0, &sst, &sc);
+      ca_finish<S, RES>(t, t + 6 * S, h, wdiff, nmax, check_only != 0, &sst, &sc);
       if (progress) __hip_atomic_store(progress, sst.it, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
@@ -1600,36 +1616,37 @@ void launch_ca_fused(const DevGeom& G, T* w, T* z0, T* z1, T* p0, T* p1, double*
 
 void launch_ca_reduce(const double* partials, int n, int n2, int s_, double h, double wdiff, int nmax,
                       bool check_only, PcgState* S, CaState* C, double* chunk, hipStream_t s, long long* progress,
-                      bool finish) {
+                      bool finish, bool residual) {
   PMX_CHECK(nmax >= 1 && nmax <= s_, "s-step PCG: a block runs 1..s iterations");
   const int nb = std::max(1, std::min(kCaReduceMaxBlocks, std::max(n, n2) / 512));
   const int co = check_only ? 1 : 0, fi = finish ? 1 : 0;
+#define PMX_CA_RED1(SS, RR)                                                                                    \
+  hipLaunchKernelGGL((k_ca_reduce1<SS, RR>), dim3(1), dim3(1024), 0, s, partials, n, n2, h, wdiff, nmax, co, fi, S, C, \
+                     progress)
+#define PMX_CA_RED(SS, RR)                                                                                     \
+  hipLaunchKernelGGL((k_ca_reduce<SS, RR>), dim3(nb), dim3(256), 0, s, partials, n, n2, h, wdiff, nmax, co, fi, S, C, \
+                     chunk, progress)
   if (std::max(n, n2) <= kCaReduce1Max) {
-    if (s_ == 2)
-      hipLaunchKernelGGL(k_ca_reduce1<2>, dim3(1), dim3(1024), 0, s, partials, n, n2, h, wdiff, nmax, co, fi, S, C,
-                         progress);
-    else
-      hipLaunchKernelGGL(k_ca_reduce1<3>, dim3(1), dim3(1024), 0, s, partials, n, n2, h, wdiff, nmax, co, fi, S, C,
-                         progress);
+    if (s_ == 2) { if (residual) PMX_CA_RED1(2, true); else PMX_CA_RED1(2, false); }
+    else { if (residual) PMX_CA_RED1(3, true); else PMX_CA_RED1(3, false); }
     HIP_CHECK(hipGetLastError());
     return;
   }
-  if (s_ == 2)
-    hipLaunchKernelGGL(k_ca_reduce<2>, dim3(nb), dim3(256), 0, s, partials, n, n2, h, wdiff, nmax, co, fi, S, C, chunk,
-                       progress);
-  else
-    hipLaunchKernelGGL(k_ca_reduce<3>, dim3(nb), dim3(256), 0, s, partials, n, n2, h, wdiff, nmax, co, fi, S, C, chunk,
-                       progress);
+  if (s_ == 2) { if (residual) PMX_CA_RED(2, true); else PMX_CA_RED(2, false); }
+  else { if (residual) PMX_CA_RED(3, true); else PMX_CA_RED(3, false); }
+#undef PMX_CA_RED
+#undef PMX_CA_RED1
   HIP_CHECK(hipGetLastError());
 }
 
 void launch_ca_finish(int s_, double h, double wdiff, int nmax, bool check_only, PcgState* S, CaState* C,
-                      hipStream_t s, long long* progress) {
+                      hipStream_t s, long long* progress, bool residual) {
   const int co = check_only ? 1 : 0;
-  if (s_ == 2)
-    hipLaunchKernelGGL(k_ca_finish<2>, dim3(1), dim3(64), 0, s, h, wdiff, nmax, co, S, C, progress);
-  else
-    hipLaunchKernelGGL(k_ca_finish<3>, dim3(1), dim3(64), 0, s, h, wdiff, nmax, co, S, C, progress);
+#define PMX_CA_FIN(SS, RR) \
+  hipLaunchKernelGGL((k_ca_finish<SS, RR>), dim3(1), dim3(64), 0, s, h, wdiff, nmax, co, S, C, progress)
+  if (s_ == 2) { if (residual) PMX_CA_FIN(2, true); else PMX_CA_FIN(2, false); }
+  else { if (residual) PMX_CA_FIN(3, true); else PMX_CA_FIN(3, false); }
+#undef PMX_CA_FIN
   HIP_CHECK(hipGetLastError());
 }
 

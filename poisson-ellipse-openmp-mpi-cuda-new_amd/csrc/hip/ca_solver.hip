@@ -78,7 +78,8 @@ void GpuSubdomainSolver::enqueue_ca_reduce(hipStream_t s, int n, bool check_only
   const int n1 = fused ? ca_tiles_.ntilesf() : ca_tiles_.ntiles();
   const int n2 = fused ? ca_tiles_.ntilesf() : ca_tiles_.ntiles2();
   launch_ca_reduce(partials_, n1, n2, ca_tiles_.s, g_.h1h2, wdiff,
-                   check_only ? 1 : n, check_only, state_, ca_state_, ca_chunk_, s, progress_dev_, finish);
+                   check_only ? 1 : n, check_only, state_, ca_state_, ca_chunk_, s, progress_dev_, finish,
+                   spec_.stop == StopRule::kResidual);
   after_launch(s);
   if (!check_only) {  // a block the device applies (unless it stopped): the set its pass 2 writes
     ++ca_blk_;
@@ -89,7 +90,8 @@ void GpuSubdomainSolver::enqueue_ca_reduce(hipStream_t s, int n, bool check_only
 void GpuSubdomainSolver::enqueue_ca_finish(hipStream_t s, int n, bool check_only) {
   PMX_CHECK(ca_, "not an s-step solver");
   const double wdiff = spec_.norm == Norm::kWeighted ? g_.h1h2 : 1.0;
-  launch_ca_finish(ca_tiles_.s, g_.h1h2, wdiff, check_only ? 1 : n, check_only, state_, ca_state_, s, progress_dev_);
+  launch_ca_finish(ca_tiles_.s, g_.h1h2, wdiff, check_only ? 1 : n, check_only, state_, ca_state_, s, progress_dev_,
+                   spec_.stop == StopRule::kResidual);
   after_launch(s);
 }
 

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <sstream>
 #include <stdexcept>
 #include <unistd.h>
 #include <string>
@@ -930,6 +931,15 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
   // and 97x130, constant rhs).  There the sweep re-reads below beta = 0.5 (growth <= 3 roundings).
   if (spec_.sigma != 0.0 && elem_ == 4 && opt_.pair_w != 2) st.pair_min_beta = 0.5;
   st.w_cycle = w_cycle();
+  // stop rule: the step rule leaves PcgState's tail zero, as every build before it did
+  stop_ref_data_ = false;
+  if (spec_.stop == StopRule::kResidual) {
+    stop_ref_data_ = !stage_w_.empty() || dev_w_ != nullptr;  // w0 given: the init reduces rho_B from the data
+    st.stop = int(StopRule::kResidual);
+    st.stop_flags = (stop_ref_data_ ? kStopRefData : 0) | (pcg1_ ? kStopRhoC : 0);
+    st.rtol = spec_.rtol;
+    st.atol = spec_.atol;
+  }
   host_k_ = st.it;
   if (progress_host_) {  // the device has finished with them: init follows a synchronised state
     for (int q = 0; q < 3; ++q) __atomic_store_n(progress_host_ + q, 0LL, __ATOMIC_RELAXED);
@@ -950,6 +960,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     X.has_f = !stage_f_.empty() || dev_f_;
     X.has_w = !stage_w_.empty() || dev_w_;
     X.sigma = spec_.sigma;
+    X.rho_b = stop_ref_data_ ? 1 : 0;
     // the same cells from either source: a staged host copy, or the caller's device block through the
     // scatter kernel (set_init_data_device)
     if (dev_f_)
@@ -978,7 +989,9 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     launch_init<T>(G, tables_, w, r, halo<T>(), partials_, init_tiles_, s, spec_.sigma);
     after_launch(s);
   }
-  launch_reduce(partials_, init_tiles_.ntiles(), 2, 0.0, g_.h1h2, state_->red_b, state_, 0, reduce_ws_, s);
+  // red_b[1] = (z^0, r^0); red_b[0] = rho_B = (D^-1 B, B) when the residual rule starts from a w0, else 0
+  launch_reduce(partials_, init_tiles_.ntiles(), 2, stop_ref_data_ ? g_.h1h2 : 0.0, g_.h1h2, state_->red_b, state_, 0,
+                reduce_ws_, s);
   after_launch(s);
   if (ca_) {  // set 0: z^0 = D^-1 r^0 (in r's buffer), p^0 = z^0; block counter 0
     std::memset(&ca_init_, 0, sizeof(CaState));
@@ -1120,6 +1133,12 @@ void GpuSubdomainSolver::phase_b_kernel_only(hipStream_t s, bool pack) {
 void GpuSubdomainSolver::enqueue_init(hipStream_t s) {
   HIP_CHECK(hipSetDevice(opt_.device));
   if (opt_.dtype == DType::kFp64) init_impl<double>(s); else init_impl<float>(s);
+}
+void GpuSubdomainSolver::enqueue_stop_init(hipStream_t s) {
+  if (spec_.stop != StopRule::kResidual) return;
+  HIP_CHECK(hipSetDevice(opt_.device));
+  launch_stop_init(state_, s);
+  after_launch(s);
 }
 void GpuSubdomainSolver::enqueue_phase_a(hipStream_t s) {
   if (opt_.dtype == DType::kFp64) phase_a_impl<double>(s); else phase_a_impl<float>(s);
@@ -1266,9 +1285,22 @@ void GpuSubdomainSolver::load_checkpoint(std::istream& is, hipStream_t s) {
     HIP_CHECK(hipMemcpy(field_raw(f), buf.data() + size_t(f) * field_bytes_, field_bytes_, hipMemcpyHostToDevice));
   is.read(buf.data(), std::streamsize(layout_.bytes));
   PMX_CHECK(is.good(), "truncated checkpoint (scalars/halos)");
-  HIP_CHECK(hipMemcpy(arena_, buf.data(), layout_.bytes, hipMemcpyHostToDevice));
   PcgState ck{};
   std::memcpy(&ck, buf.data() + layout_.state_off, sizeof(PcgState));
+  // the state carries its stop rule (files of builds without one hold zeros: the step rule)
+  const bool same_rule = ck.stop == int(spec_.stop) &&
+                         (spec_.stop == StopRule::kStep || (ck.rtol == spec_.rtol && ck.atol == spec_.atol));
+  if (!same_rule) {
+    auto show = [](int rule, double rtol, double atol) {
+      std::ostringstream o;
+      o << "stop=" << stop_rule_name(StopRule(rule));
+      if (rule == int(StopRule::kResidual)) o << " rtol=" << rtol << " atol=" << atol;
+      return o.str();
+    };
+    PMX_CHECK(false, "checkpoint was written with " << show(ck.stop, ck.rtol, ck.atol) << ", this session runs "
+                                                      << show(int(spec_.stop), spec_.rtol, spec_.atol));
+  }
+  HIP_CHECK(hipMemcpy(arena_, buf.data(), layout_.bytes, hipMemcpyHostToDevice));
   host_k_ = ck.it;
   if (pcg1_ || ca_) {
     is.read(buf.data(), std::streamsize(field_bytes_));

@@ -32,6 +32,9 @@ struct Pcg1Pro {
   long long k, max_iter;
   double rc[kNq], al[4], be[4];
   double zr0, zr1, delta, bd_tol, pmb;
+  // StopRule::kResidual (PcgState's tail): the rule and the squared threshold the init formed (k_stop_init)
+  int stop;
+  double thr2;
 };
 
 __device__ __forceinline__ Pcg1Pro pcg1_load_state(const PcgState* S) {
@@ -55,6 +58,8 @@ __device__ __forceinline__ Pcg1Pro pcg1_load_state(const PcgState* S) {
   v.max_iter = Sc->max_iter;
   v.norm = Sc->norm;
   v.cyc = Sc->w_cycle;
+  v.stop = Sc->stop;
+  v.thr2 = Sc->stop_thr2;
   return v;
 }
 
@@ -66,7 +71,7 @@ __device__ __forceinline__ void pcg1_batch(const Pcg1Pro& v, int id, unsigned lo
   asm volatile("" ::"s"(v.done), "s"(v.k), "s"(id), "s"(cls), "s"(v.rc[0]), "s"(v.rc[1]), "s"(v.rc[2]), "s"(v.rc[3]),
                "s"(v.rc[4]), "s"(v.al[0]), "s"(v.al[1]), "s"(v.al[2]), "s"(v.al[3]), "s"(v.be[0]), "s"(v.be[1]),
                "s"(v.be[2]), "s"(v.be[3]), "s"(v.zr0), "s"(v.zr1), "s"(v.delta), "s"(v.bd_tol), "s"(v.pmb),
-               "s"(v.max_iter), "s"(v.norm), "s"(v.cyc));
+               "s"(v.max_iter), "s"(v.norm), "s"(v.cyc), "s"(v.stop), "s"(v.thr2));
 }
 
 // What sweep k runs with.  wm: the w schedule of this sweep (0 = w untouched; 1 = pairs; 2 = triples
@@ -94,15 +99,21 @@ __device__ __forceinline__ bool pcg1_scalars(const Pcg1Pro& v, PcgState* S, bool
   if (k > 0) {
     const double rho = v.rc[0];  // rho_{k-1} = (z^{k-1}, r^{k-1})
     double diff = 0.0;
+    // StopRule::kResidual: iteration k-1 is tested on rho_{k-1} <= stop_thr2 = max(rtol sqrt(rho_B), atol)^2
+    // instead, a second wave-uniform branch in the same place.  The init formed the threshold and tested
+    // rho_0 (k_stop_init, pcg_kernels.hip), so no sweep writes it and sweep 1 has nothing to test.
+    const bool res = v.stop == int(StopRule::kResidual);
     if (k >= 2) {
       // stop test of iteration k-1: ||w^k - w^{k-1}|| = |alpha_{k-1}| ||p^{k-1}||
       diff = fabs(pcg1_ring4(v.al, k - 1)) * sqrt(v.rc[4]);
       const bool bad = !(diff == diff) || !(rho == rho);
-      if (bad || diff < v.delta || k > v.max_iter) {
+      const bool conv = res ? rho <= v.thr2 : diff < v.delta;
+      if (bad || conv || k > v.max_iter) {
         if (leader) {
           S->diff = diff;
+          if (res) S->stop_rho = rho;
           S->iters = k - 1;
-          S->status = bad ? int(Status::kBreakdown) : (diff < v.delta ? int(Status::kConverged) : int(Status::kMaxIter));
+          S->status = bad ? int(Status::kBreakdown) : (conv ? int(Status::kConverged) : int(Status::kMaxIter));
           if (bad) S->nan_flag = 1;
           S->done = 1;
         }
@@ -117,6 +128,7 @@ __device__ __forceinline__ bool pcg1_scalars(const Pcg1Pro& v, PcgState* S, bool
     if (bd || !(denom == denom)) {
       if (leader) {
         if (k >= 2) S->diff = diff;
+        if (res) S->stop_rho = rho;
         S->iters = k;
         S->status = int(Status::kBreakdown);
         if (!(denom == denom)) S->nan_flag = 1;

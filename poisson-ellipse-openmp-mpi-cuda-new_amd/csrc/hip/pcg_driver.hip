@@ -155,18 +155,29 @@ void PcgDriver::synchronize() {
 
 void PcgDriver::init() {
   TraceRange tr("pmx:init");
+  // residual stop rule: the last step of every init forms the threshold and tests rho_0 (k_stop_init)
+  auto stop_init = [&]() {
+    for (size_t i = 0; i < local_.size(); ++i) local_[i]->enqueue_stop_init(streams_[i]);
+  };
   if (ca_) {  // fields, state and set 0 of the first block (and its ghost rows)
     for (size_t i = 0; i < local_.size(); ++i) {
       HIP_CHECK(hipSetDevice(local_[i]->device()));
       local_[i]->enqueue_init(streams_[i]);
     }
     if (any_nb_) ca_exchange(streams_);
+    // residual stop rule: the s-step never all-reduces the init's (z^0, r^0) and rho_B otherwise (its blocks
+    // use Gram sums); then the threshold and the test of rho_0
+    if (local_[0]->spec().stop == StopRule::kResidual) comm_->allreduce(local_, 1, streams_);
+    stop_init();
     synchronize();
     return;
   }
   // pcg2's k_init packs r^0 into the send slots
   if (!single_pass_ && any_nb_) comm_->before_pack(local_, streams_);
   for (size_t i = 0; i < local_.size(); ++i) local_[i]->enqueue_init(streams_[i]);
+  // residual stop rule from a w0: rho_B's partial sums (red_b[0]) become the global one; pcg2
+  // all-reduces red_b below anyway
+  if (single_pass_ && local_[0]->stop_ref_data()) comm_->allreduce(local_, 1, streams_);
   if (single_pass_) {
     // ghosts of r^0 -> sweep 0 ((z^0, r^0), (A z^0, z^0); it 0 -> 1) -> all-reduce -> ghosts of
     // sweep 0's outputs, which sweep 1 reads
@@ -182,6 +193,7 @@ void PcgDriver::init() {
     poison(streams_);
     comm_->halo(local_, streams_);
   }
+  stop_init();
   synchronize();
 }
 
@@ -504,6 +516,11 @@ RunStats PcgDriver::solve(int poll_batches, bool do_init, int64_t ckpt_every,
   st.status = Status(s.status);
   st.diff = s.diff;
   st.nan = s.nan_flag != 0;
+  if (s.stop == int(StopRule::kResidual)) {
+    st.residual_rule = true;
+    st.residual = std::sqrt(s.stop_rho);
+    st.residual_ref = std::sqrt(s.rho_b);
+  }
   return st;
 }
 

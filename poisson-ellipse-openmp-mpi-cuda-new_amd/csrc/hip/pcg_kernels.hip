@@ -68,7 +68,7 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
   __shared__ double lds[2 * BLOCK / kWave];
   const Tile t = tile_of(blockIdx.x, tiles_j, TI, BLOCK, G);
   const int j = t.j0 + threadIdx.x;
-  double acc = 0.0, unused = 0.0;
+  double acc = 0.0, accb = 0.0;  // accb: rho_B's partial (InitData::rho_b), else 0
   if (j <= t.jend) {
     const int gj = G.gj0 + j;
     const ColConst cc = load_col(Tb, gj);
@@ -132,6 +132,7 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
         if constexpr (SH) D = add_sigma(D, X.sigma);
         const double z = (D != 0.0) ? rq / D : 0.0;
         acc += z * rq;
+        if (MODE == kInitData && X.rho_b) accb += ((D != 0.0) ? Bq / D : 0.0) * Bq;  // rho_B's partial
         r[c] = rs;
         if constexpr (MODE == kInitPlain) w[c] = T(0);
         if (i == 1 && (G.nb & kNbXlo)) H.send[0][j - 1] = rs;
@@ -141,10 +142,32 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
       }
     }
   }
-  block_sum2<BLOCK>(acc, unused, lds);
+  block_sum2<BLOCK>(acc, accb, lds);
   if (threadIdx.x == 0) {
-    partials[2 * t.id] = 0.0;
+    partials[2 * t.id] = (MODE == kInitData && X.rho_b) ? accb : 0.0;
     partials[2 * t.id + 1] = acc;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// k_stop_init (StopRule::kResidual, one lane, once per init): the threshold and the test of rho_0.
+// Runs after the init's reductions and all-reduces, so rho_0 -- red_c[0] after pcg1's sweep 0, else
+// red_b[1] -- and, after an init with w0, rho_B in red_b[0] are the global sums.  A start that already meets
+// the threshold ends the solve here: converged with 0 iterations, w = w0 untouched, nothing launched.
+// A NaN rho_0 fails the comparison and is caught by the first iteration's guards, as under the step rule.
+// ---------------------------------------------------------------------------
+__global__ void k_stop_init(PcgState* S) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const double rho0 = (S->stop_flags & kStopRhoC) ? S->red_c[0] : S->red_b[1];
+  const double rho_b = (S->stop_flags & kStopRefData) ? S->red_b[0] : rho0;
+  const double thr = fmax(S->rtol * sqrt(rho_b), S->atol);
+  S->rho_b = rho_b;
+  S->stop_rho = rho0;
+  S->stop_thr2 = thr * thr;
+  if (rho0 <= thr * thr) {
+    S->iters = 0;
+    S->status = int(Status::kConverged);
+    S->done = 1;
   }
 }
 
@@ -273,6 +296,11 @@ void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> 
         hipLaunchKernelGGL((k_init<T, B, kInitPlain>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
                            partials, tc.rows, tc.tiles_j, InitData<T>{}));
   }
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_stop_init(PcgState* S, hipStream_t s) {
+  hipLaunchKernelGGL(k_stop_init, dim3(1), dim3(64), 0, s, S);
   HIP_CHECK(hipGetLastError());
 }
 

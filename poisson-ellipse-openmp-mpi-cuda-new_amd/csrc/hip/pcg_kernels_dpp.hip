@@ -57,15 +57,19 @@ __device__ __forceinline__ bool prologue_a(PcgState* S, long long& k, bool& firs
   first = (k == 1);
   const double zr_prev = S->red_b[1];
   beta = 0.0;
+  // StopRule::kResidual: iteration k-1 is tested on rho_{k-1} = red_b[1] <= stop_thr2 instead; the init
+  // formed the threshold and tested rho_0 (k_stop_init, pcg_kernels.hip).  As pcg1_scalars (pcg1_march.hpp).
+  const bool res = S->stop == int(StopRule::kResidual);
   if (!first) {
     const double diff = sqrt(S->red_b[0]);
     const bool bad = !(diff == diff) || !(zr_prev == zr_prev);
-    if (bad || diff < S->delta || k > S->max_iter) {
+    const bool conv = res ? zr_prev <= S->stop_thr2 : diff < S->delta;
+    if (bad || conv || k > S->max_iter) {
       if (blockIdx.x == 0 && threadIdx.x == 0) {
         S->diff = diff;
+        if (res) S->stop_rho = zr_prev;
         S->iters = k - 1;
-        S->status = bad ? int(Status::kBreakdown)
-                        : (diff < S->delta ? int(Status::kConverged) : int(Status::kMaxIter));
+        S->status = bad ? int(Status::kBreakdown) : (conv ? int(Status::kConverged) : int(Status::kMaxIter));
         if (bad) S->nan_flag = 1;
         S->done = 1;
       }
@@ -320,6 +324,7 @@ k_pcg_b_wave(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, cons
   const bool bd = S->norm == int(Norm::kWeighted) ? fabs(denom) < S->bd_tol : denom < S->bd_tol;
   if (bd || !(denom == denom)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (S->stop == int(StopRule::kResidual)) S->stop_rho = S->zr[(k - 1) & 1];  // rho_{k-1}, the newest
       S->iters = k;
       S->status = int(Status::kBreakdown);
       if (!(denom == denom)) S->nan_flag = 1;
@@ -596,6 +601,7 @@ __device__ __forceinline__ void pcg_b_rows_body(const DevGeom& G, const DevTable
   const bool bd = S->norm == int(Norm::kWeighted) ? fabs(denom) < S->bd_tol : denom < S->bd_tol;
   if (bd || !(denom == denom)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (S->stop == int(StopRule::kResidual)) S->stop_rho = S->zr[(k - 1) & 1];  // rho_{k-1}, the newest
       S->iters = k;
       S->status = int(Status::kBreakdown);
       if (!(denom == denom)) S->nan_flag = 1;

@@ -24,6 +24,8 @@ struct SolveResult {
   Status status = Status::kRunning;
   double last_diff = 0.0;  // final ||w^{k+1}-w^k|| (norm per spec.norm)
   double seconds = 0.0;    // solver wall time
+  // StopRule::kResidual only (0 under the step rule): sqrt(rho) at the end and sqrt(rho_B), see spec.hpp
+  double residual = 0.0, residual_ref = 0.0;
   // solution on the global grid, (M+1) x (N+1) row-major, boundary = 0
   std::vector<double> w;
 };
@@ -54,6 +56,8 @@ class CpuSubdomain {
   double matvec_dot();                   // Ap = A p (needs p halos) -> local (Ap,p)
   void update_wr(double alpha, double* diff_local);   // w+=ap, r-=aAp, local sum dw^2
   double precond_dot();                  // z = D^-1 r -> local (z,r)
+  double rhs_dot() const;                // local (D^-1 B, B): the residual rule's reference (spec.hpp)
+  bool has_w0() const { return !w0_.empty(); }
   void update_p(double beta);            // p = z + beta p
 
   // halo access for p (the only field with halos, stage2-mpi/poisson_mpi_decomp.cpp:241-347)

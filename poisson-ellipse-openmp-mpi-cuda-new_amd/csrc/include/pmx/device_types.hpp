@@ -1,6 +1,7 @@
 // Plain-old-data structs shared by host orchestration and HIP kernels.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 namespace pmx {
@@ -82,7 +83,10 @@ struct alignas(64) PcgState {
   // exchange fills.  Written by sweep k (= k + 1) and by init (= 0) for diagnostics; the exchange
   // kernels take their target from the host (round 4), so nothing on the device reads it.
   long long halo_k;
-  long long halo_k_unpack;  // unused since round 4 (kept: checkpoint files hold PcgState)
+  // StopRule::kResidual: (z, r) of the newest tested iterate -- rho_0 from the init, then the value the stop
+  // decision was taken on.  Its own word, since the reduction buffers are still all-reduced after `done` on
+  // decomposed grids.  (The 8 bytes were halo_k_unpack, unused and zero since round 4; zero under the step rule.)
+  double stop_rho;
   // Single-pass w schedule (pcg1): w is read and written on one sweep in w_cycle (2 = pairs, 3 =
   // triples, see k_pcg1).  alpha1/beta1 hold alpha_k / beta_k at slot k & 3; w_pend_n steps
   // (p^{w_pend - w_pend_n + 1} .. p^{w_pend}, both still in the two p buffers) are not yet in w.
@@ -90,7 +94,24 @@ struct alignas(64) PcgState {
   double beta1[4];
   int w_cycle;
   int w_pend_n;
+  // Stop rule (ProblemSpec::stop), in what used to be the tail padding: the size, every offset above and the
+  // bytes of a StopRule::kStep state are unchanged (all zero here), so checkpoint files of earlier builds
+  // load as the step rule.  Under kResidual the solve ends at the first k with (z^k, r^k) <= stop_thr2.
+  int stop;         // pmx::StopRule
+  // kStopRefData: rho_B was reduced from the data by the init (w0 given) and waits in red_b[0]; else
+  // rho_B = rho_0.  kStopRhoC: the init leaves rho_0 in red_c[0] (pcg1's sweep 0), else in red_b[1].
+  int stop_flags;
+  double rtol, atol;
+  // max(rtol sqrt(rho_B), atol)^2 and rho_B: formed ONCE, by the init (k_stop_init, after the init's
+  // reductions and all-reduces), which also tests rho_0; the iteration kernels only read stop / stop_thr2
+  double stop_thr2;
+  double rho_b;
 };
+enum StopFlags : int { kStopRefData = 1, kStopRhoC = 2 };
+static_assert(sizeof(PcgState) == 320, "PcgState: the stop rule lives in the old tail padding");
+static_assert(offsetof(PcgState, w_pend_n) == 276, "PcgState: no member before the stop rule may move");
+static_assert(offsetof(PcgState, rho_b) == 312, "PcgState: the stop rule fills the tail exactly");
+static_assert(offsetof(PcgState, stop_rho) == 200, "PcgState: stop_rho takes the word of the retired halo_k_unpack");
 
 // s-step PCG (ca_kernels.hip): the per-block scalars next to PcgState.  Basis of a block: Chebyshev
 // polynomials of L = D^-1 A in p and z, Y = [P_0..P_s, Z_0..Z_{s-1}] (2s+1 vectors); p, z and w - w_k

@@ -269,6 +269,12 @@ class GpuSubdomainSolver {
   // A null argument leaves what set_init_data staged for that array in place (one array may come from
   // the host, the other from the device).
   void set_init_data_device(const double* f, const double* w0, int64_t ld_f, int64_t ld_w0);
+  // the init just enqueued reduced rho_B from the data into red_b[0] (residual stop rule with a w0): on a
+  // decomposed grid the driver all-reduces red_b before the first iteration reads it
+  bool stop_ref_data() const { return stop_ref_data_; }
+  // residual stop rule: the threshold and the test of rho_0 (k_stop_init), the last step of an init -- after
+  // every reduction and all-reduce of it.  No-op under the step rule.
+  void enqueue_stop_init(hipStream_t s);
   bool has_init_data() const { return !stage_f_.empty() || !stage_w_.empty() || dev_f_ || dev_w_; }
   // sum over the owned nodes of (B - A w)^2 for the current w (pending steps applied, as
   // download_w), B from `f` (nx x ny, null: the constant F) under the ellipse mask; w's ghost
@@ -481,6 +487,7 @@ class GpuSubdomainSolver {
   TileCfg init_tiles_{};
   // set_init_data: f / w0 in the storage type, dense, until the next init uploads them
   std::vector<char> stage_f_, stage_w_;
+  bool stop_ref_data_ = false;
   // set_init_data_device: the caller's device blocks and their row strides, until the next init
   const double* dev_f_ = nullptr;
   const double* dev_w_ = nullptr;
@@ -605,6 +612,9 @@ struct RunStats {
   double solve_seconds = 0.0;
   int64_t launched = 0;    // iterations enqueued (>= iters; the rest were device no-ops)
   bool nan = false;
+  // StopRule::kResidual only: sqrt(rho) of the last tested iterate and sqrt(rho_B) (spec.hpp)
+  bool residual_rule = false;
+  double residual = 0.0, residual_ref = 0.0;
   // per-step times (seconds, summed over the profiled iterations; only profile_phases() fills
   // them).  Mapped onto the reference's 5 buckets (stage4-mpi+cuda/poisson_mpi_cuda_f.cu:956-980)
   // by the CLI: compute = kernel_a + kernel_b, comm = allreduce + halo (incl. edge pack),

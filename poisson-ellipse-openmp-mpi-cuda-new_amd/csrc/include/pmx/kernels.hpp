@@ -103,12 +103,19 @@ struct InitData {
   const T* pb = nullptr;
   double ca = 0.0, cb = 0.0;
   int npend = 0;
+  // data init with has_w under the residual stop rule: partials[2 t] = sum over tile t of B^2 / D, the
+  // rho_B = (D^-1 B, B) the tolerance is relative to (else that slot is 0, as in every other mode)
+  int rho_b = 0;
   // screened problem (ProblemSpec::sigma): != 0 launches the kernels built for A + sigma I, D + sigma
   double sigma = 0.0;
 };
 template <typename T>
 void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
                       const TileCfg& tc, const InitData<T>& X, bool measure, hipStream_t s);
+
+// StopRule::kResidual: forms PcgState::rho_b / stop_thr2 from the init's reduced sums and tests rho_0
+// (k_stop_init).  Enqueued once per init, after its reductions and all-reduces.
+void launch_stop_init(PcgState* S, hipStream_t s);
 
 template <typename T>
 void launch_pcg_a_wave(const DevGeom& G, const DevTables& Tb, const T* r, T* p0, T* p1,
@@ -225,9 +232,10 @@ constexpr int kCaReduce1Max = 12288;
 // launch_ca_finish runs the scalars on the reduced sums afterwards
 void launch_ca_reduce(const double* partials, int n, int n2, int s_, double h, double wdiff, int nmax,
                       bool check_only, PcgState* S, CaState* C, double* chunk, hipStream_t s,
-                      long long* progress = nullptr, bool finish = true);
+                      long long* progress = nullptr, bool finish = true, bool residual = false);
+// residual (both): the kernels built for StopRule::kResidual (ca_finish<S, true>), by ProblemSpec::stop
 void launch_ca_finish(int s_, double h, double wdiff, int nmax, bool check_only, PcgState* S, CaState* C,
-                      hipStream_t s, long long* progress = nullptr);
+                      hipStream_t s, long long* progress = nullptr, bool residual = false);
 
 // pcg1 ghost exchange: pack (unpack=false) the radius-2 edges of the buffers sweep `target` reads
 // (parity of target) into H.send, or unpack H.recv into their ghost cells.

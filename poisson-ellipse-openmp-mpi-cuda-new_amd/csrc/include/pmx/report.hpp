@@ -86,6 +86,18 @@ inline void print_converged(int64_t k, double delta, bool symbolic) {
   }
 }
 
+// The rule in force: the reference's line under the step rule, the residual rule's own otherwise.
+inline void print_converged(int64_t k, const ProblemSpec& s, bool symbolic) {
+  if (s.stop == StopRule::kStep) {
+    print_converged(k, s.delta, symbolic);
+    return;
+  }
+  std::ostringstream d;
+  d << "rtol=" << s.rtol << ", atol=" << s.atol;
+  std::cout << "Converged after " << k << " iterations (stop=residual: sqrt((z,r)) <= max(rtol*sqrt((D^-1 B,B)), atol), "
+            << d.str() << ").\n";
+}
+
 struct JsonLine {
   std::ostringstream os;
   bool first = true;

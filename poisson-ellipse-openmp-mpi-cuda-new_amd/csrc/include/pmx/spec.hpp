@@ -20,6 +20,15 @@ namespace pmx {
 //  kUnweighted: sqrt(sum dw^2) < delta,        denom  < breakdown_tol (1e-15)  (stage 0)
 enum class Norm : int { kWeighted = 0, kUnweighted = 1 };
 
+// When a solve ends as converged.  kStep: the reference's rule, ||w^{k+1} - w^k|| = |alpha_k| ||p^k|| < delta.
+// kResidual: after iteration k >= 0, at the first k with sqrt(rho_k) <= max(rtol * sqrt(rho_B), atol), where
+// rho_k = (z^k, r^k), z = (D + sigma)^-1 r, and rho_B = ((D + sigma)^-1 B, B) for the masked right-hand side
+// B, both in the h1*h2-weighted inner product of the iteration's (z, r); delta is ignored.  An extension
+// without a counterpart in the reference (docs/PARITY.md).
+enum class StopRule : int { kStep = 0, kResidual = 1 };
+
+inline const char* stop_rule_name(StopRule r) { return r == StopRule::kResidual ? "residual" : "step"; }
+
 enum class Status : int { kRunning = 0, kConverged = 1, kBreakdown = 2, kMaxIter = 3 };
 
 inline const char* status_name(Status s) {
@@ -50,6 +59,10 @@ struct ProblemSpec {
   // diagonal on every interior node of the box.  0 (the reference's problem) changes nothing.  An
   // extension without a counterpart in the reference (docs/PARITY.md).
   double sigma = 0.0;
+  // Stop rule (see StopRule); rtol and atol are read under kResidual only.
+  StopRule stop = StopRule::kStep;
+  double rtol = 1e-8;
+  double atol = 0.0;
 
   int64_t effective_max_iter() const {
     return max_iter >= 0 ? max_iter : int64_t(M - 1) * int64_t(N - 1);
@@ -66,7 +79,16 @@ struct ProblemSpec {
     PMX_CHECK(delta > 0, "delta must be positive");
     PMX_CHECK(breakdown_tol >= 0, "breakdown tolerance must be >= 0");
     PMX_CHECK(std::isfinite(sigma) && sigma >= 0, "sigma must be finite and >= 0, got " << sigma);
+    PMX_CHECK(stop == StopRule::kStep || stop == StopRule::kResidual, "stop must be step or residual, got " << int(stop));
+    PMX_CHECK(std::isfinite(rtol) && rtol >= 0, "rtol must be finite and >= 0, got " << rtol);
+    PMX_CHECK(std::isfinite(atol) && atol >= 0, "atol must be finite and >= 0, got " << atol);
   }
+
+  // The residual rule's threshold on sqrt(rho) and its test: ONE copy for every host loop.  The test compares
+  // squares, rho <= thr * thr; on the device k_stop_init (pcg_kernels.hip) forms the same thr and thr * thr
+  // once per init (PcgState::stop_thr2) and the iteration kernels compare rho with it.
+  double residual_threshold(double rho_b) const { return std::max(rtol * std::sqrt(rho_b), atol); }
+  static bool residual_met(double rho, double threshold) { return rho <= threshold * threshold; }
 };
 
 // Derived grid quantities (stage0/Withoutopenmp1.cpp:107-108).

@@ -32,6 +32,12 @@ class PoissonEllipse:
     norm: str = "weighted"   # "weighted" (stages 1-4) | "unweighted" (stage 0)
     breakdown_tol: float = 1e-15     # CG guard on (Ap,p) (stage0/Withoutopenmp1.cpp:130); see spec.hpp
     sigma: float = 0.0       # screened problem (-Δ + σ) u = f, σ >= 0 constant; 0 = the reference's problem
+    # Stop rule.  "step": the reference's, ||w^{k+1} - w^k|| < delta.  "residual": the solve ends after
+    # iteration k >= 0 at the first k with sqrt(rho_k) <= max(rtol sqrt(rho_B), atol), rho_k = (z^k, r^k),
+    # z = (D + σ)^-1 r, rho_B = ((D + σ)^-1 B, B), B the masked right-hand side (spec.hpp); delta is ignored.
+    stop: str = "step"
+    rtol: float = 1e-8       # read under stop="residual" only; finite and >= 0
+    atol: float = 0.0        # likewise
 
     def __post_init__(self):
         if self.norm not in ("weighted", "unweighted"):
@@ -44,6 +50,21 @@ class PoissonEllipse:
             raise ValueError(f"sigma must be a finite number >= 0, got {self.sigma!r}") from None
         if not math.isfinite(self.sigma) or self.sigma < 0:
             raise ValueError(f"sigma must be finite and >= 0, got {self.sigma!r}")
+        if self.stop not in ("step", "residual"):
+            raise ValueError(f"stop must be step|residual, got {self.stop!r}")
+        for name in ("rtol", "atol"):
+            v = getattr(self, name)
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} must be a finite number >= 0, got {v!r}") from None
+            if not math.isfinite(v) or v < 0:
+                raise ValueError(f"{name} must be finite and >= 0, got {v!r}")
+            setattr(self, name, v)
+
+    def residual_threshold(self, rho_b: float) -> float:
+        """The residual rule's bound on sqrt(rho): max(rtol sqrt(rho_B), atol)."""
+        return max(self.rtol * math.sqrt(rho_b), self.atol)
 
     # ---- derived quantities (stage0/Withoutopenmp1.cpp:107-108) ----
     @property
@@ -71,8 +92,10 @@ class PoissonEllipse:
     def to_native(self):
         n = _native()
         s = n.ProblemSpec()
-        for f in ("M", "N", "A1", "B1", "A2", "B2", "ax", "by", "F", "delta", "breakdown_tol", "sigma"):
+        for f in ("M", "N", "A1", "B1", "A2", "B2", "ax", "by", "F", "delta", "breakdown_tol", "sigma", "rtol",
+                  "atol"):
             setattr(s, f, getattr(self, f))
+        s.stop = n.StopRule.residual if self.stop == "residual" else n.StopRule.step
         s.max_iter = -1 if self.max_iter is None else int(self.max_iter)
         s.norm = n.Norm.weighted if self.norm == "weighted" else n.Norm.unweighted
         return s

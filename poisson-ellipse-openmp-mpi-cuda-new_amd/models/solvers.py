@@ -53,7 +53,14 @@ def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
     backend rejects device tensors.
 
     problem.sigma != 0 (the screened problem (-Δ + σ) u = f): every backend solves it; hip runs pcg1 on the
-    row march at any grid size and raises ValueError for algo="ca" / "pcg2", exact=True and block_tiles=1."""
+    row march at any grid size and raises ValueError for algo="ca" / "pcg2", exact=True and block_tiles=1.
+
+    problem.stop == "residual" (PoissonEllipse.stop / rtol / atol): every backend ends at the first k >= 0 with
+    sqrt((z^k, r^k)) <= max(rtol sqrt((D^-1 B, B)), atol) -- relative to the data, also from a w0 -- and
+    reports Result.extra["residual"] / ["residual_ref"]; diff keeps the last |alpha| ||p||.  hip runs it on pcg1
+    (march and block tiles), pcg2 (exact=True included) and the s-step PCG; auto keeps its choice.  The
+    reference's absolute breakdown guard (breakdown_tol = 1e-15) fires before a tight rtol is reached on data of
+    the default size: lower it (0 = off) with such tolerances."""
     if backend in ("cpu", "serial"):
         return solve_cpu(problem, threads=1, **kw)
     if backend in ("omp", "openmp"):
@@ -70,10 +77,15 @@ def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
     raise ValueError(f"unknown backend {backend!r}")
 
 
+def _residual_extra(r) -> dict:
+    """The residual rule's report (absent under the step rule): sqrt(rho) at the end and sqrt(rho_B)."""
+    return {k: r[k] for k in ("residual", "residual_ref") if k in r}
+
+
 def solve_cpu(problem: PoissonEllipse, threads: int = 1, keep_solution: bool = True, rhs=None, w0=None) -> Result:
     r = _native().cpu_solve(problem.to_native(), int(threads), bool(keep_solution), rhs=rhs, w0=w0)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
-                  backend="cpu" if threads <= 1 else f"omp{threads}")
+                  backend="cpu" if threads <= 1 else f"omp{threads}", extra=_residual_extra(r))
 
 
 def solve_cpu_decomposed(problem: PoissonEllipse, ranks: int = 4, split: str = "reference",
@@ -82,7 +94,7 @@ def solve_cpu_decomposed(problem: PoissonEllipse, ranks: int = 4, split: str = "
     r = n.cpu_solve_decomposed(problem.to_native(), int(ranks), getattr(n.Split, split), int(threads),
                                bool(keep_solution), rhs=rhs, w0=w0)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
-                  backend="cpu-decomposed", ranks=ranks)
+                  backend="cpu-decomposed", ranks=ranks, extra=_residual_extra(r))
 
 
 def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "reference", device: int = 0,
@@ -142,6 +154,6 @@ def solve_hip(problem: PoissonEllipse, ranks: int = 1, keep_solution: bool = Tru
     r = Result(st["iters"], st["status"], st["diff"], st["solve_seconds"], w, backend="hip", ranks=ranks,
                init_seconds=st["init_seconds"],
                extra=dict(launched=st["launched"], nan=st["nan"], setup_seconds=time.perf_counter() - t0,
-                          comm=s.comm_name, grid=s.grid, device_bytes=s.device_bytes))
+                          comm=s.comm_name, grid=s.grid, device_bytes=s.device_bytes, **_residual_extra(st)))
     del s
     return r

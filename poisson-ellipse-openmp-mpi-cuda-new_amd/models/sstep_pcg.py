@@ -109,13 +109,30 @@ class TorchSStepPCG:
             Q.append(2.0 * self._lt(Q[-1]) - Q[-2])
         return Q
 
-    def init(self):
-        self.w = torch.zeros_like(self.B)
-        self.z = self.B / self.D
+    def init(self, rhs=None):
+        """rhs: optional global (M+1)x(N+1) float64 array, B = rhs inside D (0 elsewhere) in place of F."""
+        P = self.p
+        B = self.B
+        rhs = P.field(rhs, "rhs")
+        if rhs is not None:
+            sd = dict(i_start=1, i_end=P.M - 1, j_start=1, j_end=P.N - 1)
+            inside = R.inside(P, sd, self.device)[1:-1, 1:-1]
+            f = torch.as_tensor(rhs[1:-1, 1:-1].copy()).to(self.device)
+            B = torch.where(inside, f, torch.zeros_like(f))
+        self.w = torch.zeros_like(B)
+        self.z = B / self.D
         self.pv = self.z.clone()
         self.k = 0
         self.done = False
         self.status, self.iters, self.diff = "max_iter", 0, float("nan")
+        # stop="residual": the scalar lane carries rho = (z, r) = g through a block's iterations; the first j
+        # that meets the threshold ends the block, and exactly j + 1 iterations are applied (no rewind)
+        self.thr = self.rho_b = self.rho = None
+        if P.stop == "residual":
+            self.rho = self.rho_b = float((self.z * B).sum()) * P.h1 * P.h2
+            self.thr = P.residual_threshold(self.rho_b)
+            if self.rho <= self.thr * self.thr:
+                self.done, self.status = True, "converged"
 
     def block(self, nmax: int | None = None):
         """One block: up to min(s, nmax) iterations, as the device runs it -- the recurrences first
@@ -159,6 +176,11 @@ class TorchSStepPCG:
             gn = float(b @ GD @ b)
             a = b + (gn / g) * a
             g = gn
+            if self.thr is not None:
+                self.rho = g
+                if g <= self.thr * self.thr:
+                    after = ("converged", self.k + j + 1)
+                    break
         if not its:
             self.done, self.status, self.iters = True, after[0], after[1]
             return
@@ -167,7 +189,7 @@ class TorchSStepPCG:
         comb = lambda v: sum(float(v[i]) * Y[i] for i in range(n))  # noqa: E731
         for j, (alpha, aj, cj) in enumerate(its):
             self.diff = abs(alpha) * math.sqrt(float((comb(aj) ** 2).sum()) * wdiff)
-            if self.diff < P.delta:
+            if self.thr is None and self.diff < P.delta:
                 self.w = self.w + comb(cj)
                 self.k += j + 1
                 self.done, self.status, self.iters = True, "converged", self.k
@@ -185,12 +207,15 @@ class TorchSStepPCG:
             self.block(m)
             n -= m
 
-    def solve(self) -> Result:
+    def solve(self, rhs=None) -> Result:
         t0 = time.perf_counter()
-        self.init()
+        self.init(rhs=rhs)
         while not self.done:
             self.step(self.s * 16)
         g = torch.zeros(self.p.M + 1, self.p.N + 1, dtype=torch.float64)
         g[1:-1, 1:-1] = self.w.cpu()
-        return Result(self.iters, self.status, self.diff, time.perf_counter() - t0, g.numpy(),
-                      backend=f"torch-sstep{self.s}")
+        res = Result(self.iters, self.status, self.diff, time.perf_counter() - t0, g.numpy(),
+                     backend=f"torch-sstep{self.s}")
+        if self.thr is not None:
+            res.extra.update(residual=math.sqrt(max(self.rho, 0.0)), residual_ref=math.sqrt(self.rho_b))
+        return res

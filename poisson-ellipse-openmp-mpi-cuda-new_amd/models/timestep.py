@@ -13,7 +13,9 @@ class BackwardEuler:
     problem's own sigma, a reaction term).  backend "hip" keeps ONE native session for all steps
     (session_kw as make_session); a device tensor in gives a device tensor out, with no pass through
     the host.  Every other backend of solve() takes and returns NumPy arrays.  All fields are
-    (M+1) x (N+1) float64; g may be a scalar."""
+    (M+1) x (N+1) float64; g may be a scalar.  The problem's stop rule carries over: with stop="residual"
+    every step solves to rtol relative to its own right-hand side u/dt + g, not to the already small
+    residual of its start w0 = u."""
 
     def __init__(self, problem: PoissonEllipse, dt: float, backend: str = "hip", **session_kw):
         if not (isinstance(dt, (int, float)) and math.isfinite(dt) and dt > 0):
@@ -29,7 +31,7 @@ class BackwardEuler:
         rhs = u / self.dt if g is None else u / self.dt + g
         if self.session is None:
             r = solve(self.problem, self.backend, rhs=rhs, w0=u, **self.kw)
-            self.last = dict(iters=r.iters, status=r.status, diff=r.diff)
+            self.last = dict(iters=r.iters, status=r.status, diff=r.diff, **r.extra)
             return r.w
         self.last = self.session.solve(rhs=rhs, w0=u)
         on_device = hasattr(u, "__cuda_array_interface__")

@@ -69,7 +69,12 @@ class TorchPCG:
             self.r = torch.where(inside, self._local(rhs), torch.zeros_like(self.B))
             for edge in (self.r[0, :], self.r[-1, :], self.r[:, 0], self.r[:, -1]):
                 edge.zero_()
+        residual_rule = P.stop == "residual"
+        rho_b = None
         if w0 is not None:
+            if residual_rule:  # rho_B = (D^-1 B, B) while r still holds B
+                zb = R.precond(self.r, self.a, self.b, h1, h2, P.sigma)
+                rho_b = self._allsum(R.dot(zb, self.r[1:-1, 1:-1], h1, h2))
             wl = self._local(w0)  # the ring comes from the global array: no exchange
             self.r[1:-1, 1:-1] -= R.apply_A(wl, self.a, self.b, h1, h2, P.sigma)
             self.w[1:-1, 1:-1] = wl[1:-1, 1:-1]
@@ -80,6 +85,12 @@ class TorchPCG:
         self.k = 1
         self.done = False
         self.status, self.iters, self.diff = "max_iter", 0, float("nan")
+        self.rho_b = self.thr = None
+        if residual_rule:  # rho_0 is tested too: a start that is good enough ends with 0 iterations
+            self.rho_b = self.zr_old if rho_b is None else rho_b
+            self.thr = P.residual_threshold(self.rho_b)
+            if self.zr_old <= self.thr * self.thr:
+                self.done, self.status = True, "converged"
 
     def step(self, n: int = 1):
         """Run up to n iterations (no-ops once the stop rule fired, like the device flag)."""
@@ -112,7 +123,8 @@ class TorchPCG:
             dsum = self._allsum((dw * dw).sum(dtype=torch.float64))
             self.diff = math.sqrt(dsum * h1 * h2) if weighted else math.sqrt(dsum)
             self.k = k + 1
-            if self.diff < P.delta:
+            if (zr_new <= self.thr * self.thr) if self.thr is not None else (self.diff < P.delta):
+                self.zr_old = zr_new
                 self.done, self.status = True, "converged"
                 return
             beta = zr_new / self.zr_old
@@ -120,7 +132,10 @@ class TorchPCG:
             p[1:-1, 1:-1] = z + beta * p[1:-1, 1:-1]
 
     def state(self) -> dict:
-        return dict(it=self.k, done=self.done, iters=self.iters, status=self.status, diff=self.diff, nan=False)
+        d = dict(it=self.k, done=self.done, iters=self.iters, status=self.status, diff=self.diff, nan=False)
+        if self.thr is not None:
+            d.update(residual=math.sqrt(self.zr_old), residual_ref=math.sqrt(self.rho_b))
+        return d
 
     def local_error_stats(self) -> dict:
         """Unreduced (sum e^2, max |e|, max w) of this rank's block vs the analytic solution."""
@@ -144,6 +159,8 @@ class TorchPCG:
             wl = self.w[1:-1, 1:-1].to(torch.float64).cpu().numpy()
         res = Result(iters, status, diff, seconds, None, backend="torch", ranks=self.comm.world)
         res.extra["local_w"] = wl
+        if self.thr is not None:
+            res.extra.update(residual=math.sqrt(self.zr_old), residual_ref=math.sqrt(self.rho_b))
         res.extra["subdomain"] = self.sd
         if keep_solution and self.comm.world == 1:
             import numpy as np

@@ -106,6 +106,9 @@ class DistGpuPCG:
         the compute stream in a fixed order.  algo: -1 = auto (the library's choose_algo: the s-step
         PCG on big fp64 row strips where its fields fit), 1 / 2 / 3; ca_s: the s-step block size;
         split_sweep: pcg1's split sweep (-1 = the transport's default, 0 off, 1 on)."""
+        if comm == "torch" and getattr(problem, "stop", "step") != "step":
+            raise ValueError("DistGpuPCG(comm='torch'), the Python-orchestrated path, is not built for "
+                             "stop='residual': use comm='native'")
         if comm == "torch" and getattr(problem, "sigma", 0.0) != 0.0:
             raise ValueError("DistGpuPCG(comm='torch'), the Python-orchestrated path, is not built for sigma != 0: "
                              "use comm='native' or 'ipc'")
