@@ -122,7 +122,7 @@ Cli parse(int argc, char** argv) {
     } else if (a == "--exact") c.opt.exact = true;
     else if (a == "--graph-batch") c.opt.graph_batch = std::atoi(val().c_str());
     else if (a == "--tile-rows") c.opt.tile_rows = std::atoi(val().c_str());
-    else if (a == "--block") c.opt.block = std::atoi(val().c_str());
+    else if (a == "--block") (void)val();  // accepted for compatibility: the wave tiles have no such width
     else if (a == "--vec") c.opt.vec = std::atoi(val().c_str());
     else if (a == "--waves") c.opt.waves = std::atoi(val().c_str());
     else if (a == "--vec-b") c.opt.vec_b = std::atoi(val().c_str());
@@ -137,7 +137,6 @@ Cli parse(int argc, char** argv) {
     else if (a == "--kernel") {
       const std::string v = val();
       if (v != "wave") usage("--kernel wave (the round-1 lds kernels are retired)");
-      c.opt.kernel = 1;
     }
     else if (a == "--device") c.device = std::atoi(val().c_str());
     else if (a == "--dump") c.dump = val();

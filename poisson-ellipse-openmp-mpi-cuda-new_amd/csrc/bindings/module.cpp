@@ -330,10 +330,8 @@ GpuOptions make_options(int device, const std::string& kernel, int block, int ve
   o.algo = algo;
   o.device = device;
   PMX_CHECK(kernel == "wave", "kernel must be wave (the round-1 lds kernels are retired, bench/RETIRED.md), got " << kernel);
-  o.kernel = 1;
   o.vec = vec;
   o.waves = waves;
-  o.block = block;
   o.tile_rows = tile_rows;
   PMX_CHECK(dtype == "fp64" || dtype == "fp32" || dtype == "mixed",
             "dtype must be fp64, fp32 (fp32 storage and stencil arithmetic) or mixed (fp32 storage, fp64 "

@@ -19,28 +19,27 @@ namespace pmx {
 // run on a side stream, concurrently with the interior (their few long marches would otherwise trail
 // the pass by ~0.1 ms).  The first pass after a ghost exchange (pass 1 or the fused pass; with the fused
 // schedule also the batch's last pass 2) waits for it in the tiles that read ghost rows.
-template <typename T>
-void GpuSubdomainSolver::ca_pass_impl(hipStream_t s, int kind) {
-  T* w = static_cast<T*>(field_base(0));
-  T* z0 = static_cast<T*>(field_base(1));
-  T* z1 = reinterpret_cast<T*>(r2_ + field_off_ * elem_);
-  T* p0 = static_cast<T*>(field_base(2));
-  T* p1 = static_cast<T*>(field_base(3));
+void GpuSubdomainSolver::ca_pass(hipStream_t s, int kind) {
   hipEvent_t wait = ca_frame_wait_;
   ca_frame_wait_ = nullptr;
   auto launch = [&](hipStream_t side) {
-    if (kind == 2)
-      launch_ca_fused<T>(ca_geom_, w, z0, z1, p0, p1, partials_, ca_state_, ca_tiles_, s, side, wait);
-    else
-      launch_ca_sweep<T>(ca_geom_, ca_tables_, w, z0, z1, p0, p1, partials_, state_, ca_state_, ca_tiles_, kind == 1,
-                         s, side, wait);
+    with_storage([&](auto t) {
+      using T = decltype(t);
+      const Fields<T> F = fields<T>();  // r, r2: the two z buffers
+      if (kind == 2)
+        launch_ca_fused<T>(ca_geom_, F.w, F.r, F.r2, F.p0, F.p1, partials_.get(), ca_state_.get(), ca_tiles_, s, side,
+                           wait);
+      else
+        launch_ca_sweep<T>(ca_geom_, ca_tables_, F.w, F.r, F.r2, F.p0, F.p1, partials_.get(), state_, ca_state_.get(),
+                           ca_tiles_, kind == 1, s, side, wait);
+    });
   };
   if (ca_side_) {
-    HIP_CHECK(hipEventRecord(ca_ev_fork_, s));
-    HIP_CHECK(hipStreamWaitEvent(ca_side_, ca_ev_fork_, 0));
-    launch(ca_side_);
-    HIP_CHECK(hipEventRecord(ca_ev_join_, ca_side_));
-    HIP_CHECK(hipStreamWaitEvent(s, ca_ev_join_, 0));
+    HIP_CHECK(hipEventRecord(ca_ev_fork_.get(), s));
+    HIP_CHECK(hipStreamWaitEvent(ca_side_.get(), ca_ev_fork_.get(), 0));
+    launch(ca_side_.get());
+    HIP_CHECK(hipEventRecord(ca_ev_join_.get(), ca_side_.get()));
+    HIP_CHECK(hipStreamWaitEvent(s, ca_ev_join_.get(), 0));
   } else {
     launch(nullptr);
   }
@@ -50,24 +49,20 @@ void GpuSubdomainSolver::ca_pass_impl(hipStream_t s, int kind) {
 void GpuSubdomainSolver::drop_side_stream() {
   if (!ca_side_) return;
   HIP_CHECK(hipSetDevice(opt_.device));
-  HIP_CHECK(hipStreamSynchronize(ca_side_));
-  HIP_CHECK(hipStreamDestroy(ca_side_));
-  HIP_CHECK(hipEventDestroy(ca_ev_fork_));
-  HIP_CHECK(hipEventDestroy(ca_ev_join_));
-  ca_side_ = nullptr;
-  ca_ev_fork_ = ca_ev_join_ = nullptr;
+  HIP_CHECK(hipStreamSynchronize(ca_side_.get()));
+  ca_side_.reset();
+  ca_ev_fork_.reset();
+  ca_ev_join_.reset();
 }
 
 void GpuSubdomainSolver::enqueue_ca_pass(hipStream_t s, bool upd) {
   PMX_CHECK(ca_, "not an s-step solver");
-  if (elem_ == 8) ca_pass_impl<double>(s, upd ? 1 : 0);
-  else ca_pass_impl<float>(s, upd ? 1 : 0);
+  ca_pass(s, upd ? 1 : 0);
 }
 
 void GpuSubdomainSolver::enqueue_ca_fused(hipStream_t s) {
   PMX_CHECK(ca_fused(), "not an s-step solver with the fused pass");
-  if (elem_ == 8) ca_pass_impl<double>(s, 2);
-  else ca_pass_impl<float>(s, 2);
+  ca_pass(s, 2);
 }
 
 void GpuSubdomainSolver::enqueue_ca_reduce(hipStream_t s, int n, bool check_only, bool finish, bool fused) {
@@ -77,8 +72,8 @@ void GpuSubdomainSolver::enqueue_ca_reduce(hipStream_t s, int n, bool check_only
   // after the fused pass both the Gram products and the norms come from its tiling
   const int n1 = fused ? ca_tiles_.ntilesf() : ca_tiles_.ntiles();
   const int n2 = fused ? ca_tiles_.ntilesf() : ca_tiles_.ntiles2();
-  launch_ca_reduce(partials_, n1, n2, ca_tiles_.s, g_.h1h2, wdiff,
-                   check_only ? 1 : n, check_only, state_, ca_state_, ca_chunk_, s, progress_dev_, finish,
+  launch_ca_reduce(partials_.get(), n1, n2, ca_tiles_.s, g_.h1h2, wdiff, check_only ? 1 : n, check_only, state_,
+                   ca_state_.get(), ca_chunk_.get(), s, progress_dev_, finish,
                    spec_.stop == StopRule::kResidual);
   after_launch(s);
   if (!check_only) {  // a block the device applies (unless it stopped): the set its pass 2 writes
@@ -90,31 +85,31 @@ void GpuSubdomainSolver::enqueue_ca_reduce(hipStream_t s, int n, bool check_only
 void GpuSubdomainSolver::enqueue_ca_finish(hipStream_t s, int n, bool check_only) {
   PMX_CHECK(ca_, "not an s-step solver");
   const double wdiff = spec_.norm == Norm::kWeighted ? g_.h1h2 : 1.0;
-  launch_ca_finish(ca_tiles_.s, g_.h1h2, wdiff, check_only ? 1 : n, check_only, state_, ca_state_, s, progress_dev_,
-                   spec_.stop == StopRule::kResidual);
+  launch_ca_finish(ca_tiles_.s, g_.h1h2, wdiff, check_only ? 1 : n, check_only, state_, ca_state_.get(), s,
+                   progress_dev_, spec_.stop == StopRule::kResidual);
   after_launch(s);
 }
 
 GpuSubdomainSolver::CaProbe GpuSubdomainSolver::ca_probe(const std::vector<double>& z, const std::vector<double>& p,
                                                          const std::vector<double>& w, const std::vector<double>& coef,
                                                          const std::vector<double>& pa, bool fused, hipStream_t s) {
-  PMX_CHECK(ca_ && elem_ == 8, "ca_probe: not an fp64 s-step solver");
+  PMX_CHECK(ca_ && plan_.elem == 8, "ca_probe: not an fp64 s-step solver");
   PMX_CHECK(!fused || ca_fused(), "ca_probe: the fused pass runs undecomposed grids");
   const int S = ca_tiles_.s, NB = 2 * S + 1, NQ = 6 * S;
-  const size_t rows = size_t(sd_.nx + 2 * gh_), cols = size_t(sd_.ny + 2);
+  const size_t rows = size_t(sd_.nx + 2 * plan_.gh), cols = size_t(sd_.ny + 2);
   PMX_CHECK(z.size() == rows * cols && p.size() == rows * cols && w.size() == rows * cols,
             "ca_probe: fields must be (nx + 2 gh) x (ny + 2)");
   PMX_CHECK(coef.size() == size_t(3 * NB) && pa.size() == size_t(S * NB), "ca_probe: coefficient shapes");
   HIP_CHECK(hipSetDevice(opt_.device));
   enqueue_init(s);
   HIP_CHECK(hipStreamSynchronize(s));
-  auto put = [&](void* base, const std::vector<double>& v) {
-    char* dst = static_cast<char*>(base) + int64_t(1 - gh_) * geom_.pitch * 8;
-    HIP_CHECK(hipMemcpy2D(dst, size_t(geom_.pitch) * 8, v.data(), cols * 8, cols * 8, rows, hipMemcpyHostToDevice));
+  auto put = [&](int f, const std::vector<double>& v) {  // local rows 1-gh .. nx+gh, columns 0 .. ny+1
+    HIP_CHECK(hipMemcpy2D(field_ptr(f, 1 - plan_.gh), plan_.row_bytes(), v.data(), cols * 8, cols * 8, rows,
+                          hipMemcpyHostToDevice));
   };
-  put(field_base(1), z);
-  put(field_base(2), p);
-  put(field_base(0), w);
+  put(1, z);
+  put(2, p);
+  put(0, w);
   CaProbe out;
   auto sums = [&](int64_t base, int nq, int n) {
     const std::vector<double> h = read_partials(s);
@@ -124,7 +119,7 @@ GpuSubdomainSolver::CaProbe GpuSubdomainSolver::ca_probe(const std::vector<doubl
     return r;
   };
   CaState c{};
-  HIP_CHECK(hipMemcpy(&c, ca_state_, sizeof(CaState), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(&c, ca_state_.get(), sizeof(CaState), hipMemcpyDeviceToHost));
   c.blk = 1;  // as after the block's reduction: pass 2 / the fused pass read set 0, write set 1
   c.nupd = S;
   for (int k = 0; k < 3; ++k)
@@ -135,28 +130,27 @@ GpuSubdomainSolver::CaProbe GpuSubdomainSolver::ca_probe(const std::vector<doubl
     enqueue_ca_pass(s, false);
     HIP_CHECK(hipStreamSynchronize(s));
     out.gram = sums(0, NQ, ca_tiles_.ntiles());
-    HIP_CHECK(hipMemcpy(ca_state_, &c, sizeof(CaState), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(ca_state_.get(), &c, sizeof(CaState), hipMemcpyHostToDevice));
     enqueue_ca_pass(s, true);
     HIP_CHECK(hipStreamSynchronize(s));
     out.norms = sums(int64_t(NQ) * ca_tiles_.ntiles(), S, ca_tiles_.ntiles2());
   } else {
-    HIP_CHECK(hipMemcpy(ca_state_, &c, sizeof(CaState), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(ca_state_.get(), &c, sizeof(CaState), hipMemcpyHostToDevice));
     enqueue_ca_fused(s);
     HIP_CHECK(hipStreamSynchronize(s));
     const std::vector<double> gn = sums(0, NQ + S, ca_tiles_.ntilesf());
     out.gram.assign(gn.begin(), gn.begin() + NQ);
     out.norms.assign(gn.begin() + NQ, gn.end());
   }
-  auto get = [&](const void* base) {
+  auto get = [&](int f) {  // the owned nodes
     std::vector<double> h(size_t(sd_.nx) * sd_.ny);
-    const char* src = static_cast<const char*>(base) + (geom_.pitch + 1) * 8;
-    HIP_CHECK(hipMemcpy2D(h.data(), size_t(sd_.ny) * 8, src, size_t(geom_.pitch) * 8, size_t(sd_.ny) * 8,
+    HIP_CHECK(hipMemcpy2D(h.data(), size_t(sd_.ny) * 8, field_ptr(f, 1, 1), plan_.row_bytes(), size_t(sd_.ny) * 8,
                           size_t(sd_.nx), hipMemcpyDeviceToHost));
     return h;
   };
-  out.p = get(field_base(3));
-  out.z = get(r2_ + field_off_ * elem_);
-  out.w = get(field_base(0));
+  out.p = get(3);
+  out.z = get(4);
+  out.w = get(0);
   return out;
 }
 
@@ -167,19 +161,12 @@ HaloMsgs GpuSubdomainSolver::ca_halo_msgs(int set) const {
   // & 1, mirrored by ca_blk_) into the neighbour's gh ghost rows (gh = s, 2s with the fused pass), as
   // ONE span per field: rows q .. q+gh-2 whole, row q+gh-1's columns 0 .. ny+1 (columns <= 0 and >= ny+1
   // are Dirichlet on a strip)
-  const int s = gh_;
-  char* fz = set ? r2_ + field_off_ * elem_ : static_cast<char*>(field_base(1));
-  char* fp = static_cast<char*>(field_base(set ? 3 : 2));
-  const int64_t P = geom_.pitch;
-  const int count = int((s - 1) * P + sd_.ny + 2);
+  const int gh = plan_.gh;
   for (int slot = 0; slot < 2; ++slot) {
     if (layout_.peer[slot] < 0) continue;
-    const int64_t srow = slot == 0 ? 1 : sd_.nx - s + 1, rrow = slot == 0 ? 1 - s : sd_.nx + 1;
-    for (int f = 0; f < 2; ++f) {
-      char* base = f == 0 ? fz : fp;
-      out.m[out.n++] = HaloMsg{slot, f, layout_.peer[slot], count, base + srow * P * int64_t(elem_),
-                               base + rrow * P * int64_t(elem_)};
-    }
+    const int64_t srow = slot == 0 ? 1 : sd_.nx - gh + 1, rrow = slot == 0 ? 1 - gh : sd_.nx + 1;
+    out.m[out.n++] = row_msg(slot, 0, set ? 4 : 1, gh, srow, rrow);
+    out.m[out.n++] = row_msg(slot, 1, set ? 3 : 2, gh, srow, rrow);
   }
   return out;
 }

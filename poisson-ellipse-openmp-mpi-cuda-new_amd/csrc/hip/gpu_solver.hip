@@ -35,6 +35,26 @@ size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+template <typename T> DevPtr<T> dev_alloc(size_t bytes) {
+  T* p = nullptr;
+  HIP_CHECK(hipMalloc(&p, bytes));
+  return DevPtr<T>(p);
+}
+Stream make_stream() {
+  hipStream_t s = nullptr;
+  HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  return Stream(s);
+}
+template <typename T> HostPtr<T> host_alloc(size_t bytes, unsigned flags) {
+  T* p = nullptr;
+  HIP_CHECK(hipHostMalloc(&p, bytes, flags));
+  return HostPtr<T>(p);
+}
+Event make_event(unsigned flags = hipEventDefault) {
+  hipEvent_t e = nullptr;
+  HIP_CHECK(hipEventCreateWithFlags(&e, flags));
+  return Event(e);
+}
 }  // namespace
 
 DevGeom make_dev_geom(const ProblemSpec& spec, const Subdomain& sd, int64_t pitch) {
@@ -65,7 +85,7 @@ DevTables upload_tables(const ProblemSpec& spec, double** owner) {
   const geo::FaceTables ft(spec, g);
   const size_t nxT = spec.M + 2, nyT = spec.N + 2;
   const size_t ndbl = 4 * nxT + 4 * nyT, nint = 8 * nxT;
-  HIP_CHECK(hipMalloc(owner, ndbl * sizeof(double) + nint * sizeof(int)));
+  DevPtr<double> buf = dev_alloc<double>(ndbl * sizeof(double) + nint * sizeof(int));
   std::vector<double> host(ndbl);
   double* h = host.data();
   std::memcpy(h + 0 * nxT, ft.rv.data(), nxT * 8);
@@ -77,10 +97,10 @@ DevTables upload_tables(const ProblemSpec& spec, double** owner) {
   std::memcpy(hy + 1 * nyT, ft.ylo.data(), nyT * 8);
   std::memcpy(hy + 2 * nyT, ft.yhi.data(), nyT * 8);
   std::memcpy(hy + 3 * nyT, ft.y.data(), nyT * 8);
-  HIP_CHECK(hipMemcpy(*owner, host.data(), ndbl * 8, hipMemcpyHostToDevice));
-  const double* d = *owner;
+  HIP_CHECK(hipMemcpy(buf.get(), host.data(), ndbl * 8, hipMemcpyHostToDevice));
+  const double* d = buf.get();
   const double* dy = d + 4 * nxT;
-  int* cls = reinterpret_cast<int*>(*owner + ndbl);
+  int* cls = reinterpret_cast<int*>(buf.get() + ndbl);
   DevTables T{d, d + nxT, d + 2 * nxT, d + 3 * nxT, dy, dy + nyT, dy + 2 * nyT, dy + 3 * nyT,
               cls, cls + 4 * nxT};
   // classify every row on the device with the exact coefficient formulas
@@ -88,6 +108,7 @@ DevTables upload_tables(const ProblemSpec& spec, double** owner) {
   whole.M = spec.M; whole.N = spec.N; whole.nx = spec.M - 1; whole.ny = spec.N - 1;
   launch_classify(make_dev_geom(spec, whole, spec.N + 2), T, cls, cls + 4 * nxT, nullptr);
   HIP_CHECK(hipDeviceSynchronize());
+  *owner = buf.release();
   return T;
 }
 
@@ -202,7 +223,6 @@ void apply_sigma_rules(const ProblemSpec& spec, const ProcGrid& grid, GpuOptions
   if (o.algo == 2) refuse("algo=\"pcg2\"");
   if (o.exact) refuse("exact=True (the reference's operation order)");
   if (o.block1 == 1) refuse("block_tiles=1");
-  if (o.kernel != 1) refuse("a kernel other than the wave tiles");
   if (grid.size() > 1 && ((spec.M - 1) / grid.Px < 2 || (spec.N - 1) / grid.Py < 2))
     refuse("a decomposition into subdomains thinner than 2 nodes");
   o.algo = 1;
@@ -215,9 +235,8 @@ bool choose_single_pass(const ProblemSpec& spec, const ProcGrid& grid, const Gpu
   if (o.algo == 2 || o.algo == 3) return false;
   // the radius-2 halo takes two owned lines from every neighbour: each block needs >= 2 x 2
   const bool thick = grid.size() == 1 || ((spec.M - 1) / grid.Px >= 2 && (spec.N - 1) / grid.Py >= 2);
-  const bool ok = !o.exact && o.kernel == 1 && thick;
-  PMX_CHECK(o.algo != 1 || ok,
-            "pcg1 needs the wave kernels, the fast arithmetic and subdomains of at least 2 x 2 nodes");
+  const bool ok = !o.exact && thick;
+  PMX_CHECK(o.algo != 1 || ok, "pcg1 needs the fast arithmetic and subdomains of at least 2 x 2 nodes");
   if (o.algo == 1) return true;
   // auto: every storage type.  (Round 1 kept pcg2 for fp32 -- 32768^2: pcg1 8.99 ms vs pcg2 7.69 --
   // but with the scalar-cache row tables and short tiles pcg1 wins there too: 5.20 vs 7.08 ms,
@@ -225,7 +244,7 @@ bool choose_single_pass(const ProblemSpec& spec, const ProcGrid& grid, const Gpu
   if (!ok) return false;
   if (device_total_bytes > 0) {  // the 5th field must fit (rank 0 holds the largest block)
     const Subdomain sd0 = decompose_2d(spec.M, spec.N, grid, 0);
-    const double need = double(GpuSubdomainSolver::estimate_device_bytes(spec, sd0, o.dtype, true)) *
+    const double need = double(GpuSubdomainSolver::estimate_device_bytes_algo(spec, sd0, o.dtype, 1)) *
                         std::max(1, subdomains_per_device);
     if (need > 0.95 * device_total_bytes) return false;
   }
@@ -243,7 +262,7 @@ int choose_algo(const ProblemSpec& spec, const ProcGrid& grid, const GpuOptions&
                                              (grid.Py == 1 || (spec.N - 1) / grid.Py >= 8));
     // every storage type: with fp32 / mixed fields the s-step keeps its basis and sums in fp64 registers
     // and beats pcg1 too (16384^2 0.951 vs 1.093 ms, 32768^2 3.356 vs 3.831; NOTES #124)
-    bool ca = !o.exact && o.kernel == 1 && strips && int64_t(spec.M - 1) * (spec.N - 1) >= kCaAutoPoints;
+    bool ca = !o.exact && strips && int64_t(spec.M - 1) * (spec.N - 1) >= kCaAutoPoints;
     if (ca && device_total_bytes > 0) {  // rank 0 holds the largest strip
       const Subdomain sd0 = decompose_2d(spec.M, spec.N, grid, 0);
       const double need = double(GpuSubdomainSolver::estimate_device_bytes_algo(spec, sd0, o.dtype, 3)) *
@@ -289,21 +308,13 @@ GpuSubdomainSolver::GpuSubdomainSolver(const ProblemSpec& spec, const Subdomain&
   PMX_CHECK(sd.nx >= 1 && sd.ny >= 1, "empty subdomain");
   apply_sigma_rules(spec_, sd_.grid, opt_);
   HIP_CHECK(hipSetDevice(opt_.device));
-  try {
-    construct(external_arena);
-  } catch (...) {
-    release();  // the destructor does not run for a throwing constructor
-    throw;
-  }
+  construct(external_arena);  // if it throws, the members' owners free what it had allocated
 }
-
 
 void GpuSubdomainSolver::construct(uintptr_t external_arena) {
   const GpuOptions& opt = opt_;
   const ProblemSpec& spec = spec_;
   const Subdomain& sd = sd_;
-  elem_ = opt.dtype == DType::kFp64 ? 8 : 4;
-  const size_t align_elems = 256 / elem_;
   size_t free_b = 0, total_b = 0;
   HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
 
@@ -323,23 +334,13 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
   ca_fuse_ = ca_ && (opt_.ca_fuse == 1 || (opt_.ca_fuse == -1 && fuse_ok));
   // ghost rows per side: 2 (the single-pass radius-2 halo); a decomposed s-step subdomain needs s, 2s with
   // the fused pass (rows, and columns on 2-D blocks)
-  gh_ = ca_ && sd.grid.size() > 1 ? (ca_fuse_ ? 2 * opt_.ca_s : opt_.ca_s) : 2;
-  const bool ca_cols = ca_ && sd.grid.Py > 1;  // ghost columns: gh_ per side
-  PMX_CHECK(!pcg1_ || (!opt.exact && opt.kernel == 1 && (sd.grid.size() == 1 || (sd.nx >= 2 && sd.ny >= 2))),
-            "pcg1 needs the wave kernels, the fast arithmetic and a subdomain of at least 2 x 2 nodes");
-
-  // +8 columns of padding: vector loads of VEC <= 4 columns starting at <= ny+3 stay in the row,
-  // and the last padding element of a row is column -1 of the next one
-  // (s-step blocks: + 2 gh + 8, so that the right ghost columns ny+1 .. ny+gh of a row and the left ones of
-  // the next row -- that row's padding read as columns -gh .. -1 -- never overlap)
-  geom_ = make_dev_geom(spec, sd,
-                        int64_t(round_up(size_t(sd.ny + 2 + 8 + (ca_cols ? 2 * gh_ + 8 : 0)), align_elems)));
+  const int gh = ca_ && sd.grid.size() > 1 ? (ca_fuse_ ? 2 * opt_.ca_s : opt_.ca_s) : 2;
+  PMX_CHECK(!pcg1_ || (!opt.exact && (sd.grid.size() == 1 || (sd.nx >= 2 && sd.ny >= 2))),
+            "pcg1 needs the fast arithmetic and a subdomain of at least 2 x 2 nodes");
+  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh);
+  const int elem = int(plan_.elem);
+  geom_ = make_dev_geom(spec, sd, plan_.pitch);
   const DevGeom& G = geom_;
-
-  // fields: element (li, lj), li = -1 .. nx+2, at base[li*pitch + lj]; base = alloc + pitch +
-  // (align-1) so that every interior row starts 256-B aligned (lj = 1)
-  field_off_ = size_t(gh_ - 1) * size_t(G.pitch) + align_elems - 1;
-  field_bytes_ = round_up((align_elems - 1 + size_t(sd.nx + 2 * gh_) * G.pitch) * elem_, 256);
   {  // fail with a sizing message instead of a bare hipErrorOutOfMemory
     const size_t need = estimate_device_bytes_algo(spec, sd, opt.dtype, opt_.algo);
     PMX_CHECK(need <= free_b,
@@ -350,19 +351,19 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
                               "device is ~"
                            << max_square_grid(double(total_b), 1, opt.dtype) << "^2 (pmx --plan)");
   }
-  // One allocation for all fields (field f at fields_ + f * field_bytes_).  The offset between the
-  // fields (0 ... 8 MiB of stagger) and physically contiguous memory were measured: no gain
-  // (profiles/r3/placement/stagger.log); where the block lands is what matters (place_fields).
-  field_stride_ = field_bytes_;
-  const int nfields = pcg1_ || ca_ ? 5 : 4;
-  HIP_CHECK(hipMalloc(&fields_, size_t(nfields) * field_stride_));
+  // One allocation for all fields.  The offset between the fields (0 ... 8 MiB of stagger) and
+  // physically contiguous memory were measured: no gain (profiles/r3/placement/stagger.log); where the
+  // block lands is what matters (place_fields).
+  fields_ = dev_alloc<char>(plan_.fields_total());
   if (const char* e = std::getenv("PMX_DEBUG_ALLOC"); e && e[0] == '1')
-    std::fprintf(stderr, "pmx alloc: fields %p (%zu B, mod 1G %zu, mod 2M %zu)\n", static_cast<void*>(fields_),
-                 size_t(nfields) * field_stride_, size_t(reinterpret_cast<uintptr_t>(fields_) % (size_t(1) << 30)),
-                 size_t(reinterpret_cast<uintptr_t>(fields_) % (size_t(1) << 21)));
+    std::fprintf(stderr, "pmx alloc: fields %p (%zu B, mod 1G %zu, mod 2M %zu)\n", static_cast<void*>(fields_.get()),
+                 plan_.fields_total(), size_t(reinterpret_cast<uintptr_t>(fields_.get()) % (size_t(1) << 30)),
+                 size_t(reinterpret_cast<uintptr_t>(fields_.get()) % (size_t(1) << 21)));
 
   // 1D face tables
-  tables_ = upload_tables(spec, &tables_buf_);
+  double* tables_buf = nullptr;
+  tables_ = upload_tables(spec, &tables_buf);
+  tables_buf_.reset(tables_buf);
   ca_geom_ = geom_;
   ca_tables_ = tables_;
   if (ca_ && opt_.ca_dirichlet) {  // see ca_tables_
@@ -378,12 +379,11 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
     ca_tables_.acls += 4 * o;
     ca_tables_.bcls += 4 * o;
   }
-  ca_gh_ = ca_geom_.nb ? gh_ : 2;
+  ca_gh_ = ca_geom_.nb ? gh : 2;
 
-  PMX_CHECK(opt.kernel == 1, "kernel must be 1 (wave tiles); the round-1 LDS-ring kernels are retired (bench/RETIRED.md)");
   // tile shapes per kernel (profiles/tile_counters_16384_fp64.md: pcg_a is fastest with 4
   // columns/lane, pcg_b with 2 in fp64; fp32 moves 16 B with 4 columns)
-  const bool fp64 = opt.dtype == DType::kFp64;
+  const bool fp64 = elem == 8;
   const int vec_a = opt.vec ? opt.vec : (opt.waves == 4 ? 4 : 2);  // (4, 4) is instantiated
   const int vec_b = opt.vec_b ? opt.vec_b : opt.vec ? opt.vec : (fp64 || opt.waves != 4 ? 2 : 4);
   const int waves_b = opt.waves_b ? opt.waves_b : opt.waves;
@@ -405,7 +405,7 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
     // forces it, PMX_PCG1_BLOCK_ROWS=4|8|12|16 and PMX_PCG1_BLOCK_WAVES=8|16 pick the shape.
     const int blk = opt_.block1;
     const int64_t t4 = int64_t((G.nx + 3) / 4) * ((G.ny + 123) / 124);
-    if (G.nb == 0 && elem_ == 8 && (blk == 1 || (blk == -1 && t4 < 10000))) {
+    if (G.nb == 0 && elem == 8 && (blk == 1 || (blk == -1 && t4 < 10000))) {
       const int rows = opt_.block_rows1 ? opt_.block_rows1 : t4 < 1000 ? 8 : 12;
       PMX_CHECK(pcg1_block_shape_ok(rows, opt_.block_waves1),
                 "block tiles: no " << rows << "-row x " << opt_.block_waves1 << "-wave variant");
@@ -423,76 +423,72 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
       opt_.waves1w = 1;
       opt_.pf1 = opt_.pf1w = 1;
     }
-    tiles1_ = make_pcg1_tiles(G, opt_.vec1, opt_.waves1, opt_.rows1, opt_.pf1, int(elem_));
+    tiles1_ = make_pcg1_tiles(G, opt_.vec1, opt_.waves1, opt_.rows1, opt_.pf1, elem);
 #ifdef PMX_WAVE_TRACE
     if (const char* e = std::getenv("PMX_WAVE_TRACE_IT"); e && e[0]) {
       wtrace_n_ = tiles1_.ntiles();
       wtrace_ = pcg1_wave_trace_setup(std::atoll(e), wtrace_n_);
     }
 #endif
-    r2_ = field_raw(4);
-    tiles1_.arith32 = elem_ == 4 && opt_.arith32 ? 1 : 0;
+    tiles1_.arith32 = elem == 4 && opt_.arith32 ? 1 : 0;
     const int waves_w = opt_.waves1w ? opt_.waves1w : (opt_.waves1 == 8 ? 4 : opt_.waves1);
     tiles1w_ = make_pcg1_tiles(G, opt_.vec1, waves_w, opt_.rows1w ? opt_.rows1w : tiles1_.rows,
-                               opt_.pf1w ? opt_.pf1w : tiles1_.pf, int(elem_));
+                               opt_.pf1w ? opt_.pf1w : tiles1_.pf, elem);
     tiles1w_.arith32 = tiles1_.arith32;
     tiles1_.lds_pad = pcg1_lds_pad(opt_.wpcu1, tiles1_.waves);
     tiles1w_.lds_pad = pcg1_lds_pad(opt_.wpcu1w, tiles1w_.waves);
     if (block1_) tiles1_.bwaves = tiles1w_.bwaves = opt_.block_waves1;
     // the LDS-DMA march: fp64 with the default shape only (VEC 2, 1 wave, register prefetch 1)
-    auto dma_ok = [&](const TileCfg& t) { return elem_ == 8 && t.vec == 2 && t.waves == 1 && t.pf == 1; };
+    auto dma_ok = [&](const TileCfg& t) { return elem == 8 && t.vec == 2 && t.waves == 1 && t.pf == 1; };
     if (dma_ok(tiles1_)) tiles1_.dpf = opt_.dma1;
     if (dma_ok(tiles1w_)) tiles1w_.dpf = opt_.dma1w >= 0 ? opt_.dma1w : opt_.dma1;
     const bool same_w = tiles1w_.rows == tiles1_.rows && tiles1w_.waves == tiles1_.waves;
     // dispatch order tables with the tiles' row classes; order1: the ellipse-cut tiles first
     // within each XCD's share (their 3-5x longer tiles would trail the sweep)
-    HIP_CHECK(hipMalloc(&tile_order_, pcg1_order_slots(tiles1_) * sizeof(Pcg1Slot)));
-    slow_tiles_ = pcg1_build_order(G, tables_, tiles1_, tile_order_, opt_.order1 != 0, nullptr);
+    tile_order_ = dev_alloc<Pcg1Slot>(pcg1_order_slots(tiles1_) * sizeof(Pcg1Slot));
+    slow_tiles_ = pcg1_build_order(G, tables_, tiles1_, tile_order_.get(), opt_.order1 != 0, nullptr);
     if (same_w) {
       tiles1w_.order0 = tiles1_.order0;
       tiles1w_.order1 = tiles1_.order1;
       tiles1w_.order2 = tiles1_.order2;
       for (int q = 0; q < 3; ++q) tiles1w_.groups[q] = tiles1_.groups[q];
     } else {
-      HIP_CHECK(hipMalloc(&tile_order_w_, pcg1_order_slots(tiles1w_) * sizeof(Pcg1Slot)));
-      (void)pcg1_build_order(G, tables_, tiles1w_, tile_order_w_, opt_.order1 != 0, nullptr);
+      tile_order_w_ = dev_alloc<Pcg1Slot>(pcg1_order_slots(tiles1w_) * sizeof(Pcg1Slot));
+      (void)pcg1_build_order(G, tables_, tiles1w_, tile_order_w_.get(), opt_.order1 != 0, nullptr);
     }
   }
 
   if (ca_) {
-    r2_ = field_raw(4);  // the second z buffer
     ca_tiles_ = make_ca_tiles(ca_geom_, opt_.ca_s, opt_.ca_rows, opt_.ca_rows2, opt_.ca_rows_f);
     ca_tiles_.fuse = ca_fuse_ ? 1 : 0;
     if (const char* e = study_env("PMX_CA_SPLIT_F"); e && e[0]) ca_tiles_.split_f = std::atoi(e);
     // the face coefficients of every node, read on the rows the ellipse cuts (2 more field-sized arrays)
     // fp64 whatever the fields' storage, in the fields' pitch (elements); column 1 of every row 256-B aligned
-    const size_t face_off = size_t(gh_ - 1) * size_t(geom_.pitch) + 31;
-    ca_face_bytes_ = round_up((31 + size_t(sd.nx + 2 * gh_) * size_t(geom_.pitch)) * 8, 256);
-    HIP_CHECK(hipMalloc(&ca_faces_, 2 * ca_face_bytes_));
-    ca_tiles_.fa = reinterpret_cast<const double*>(ca_faces_ + face_off * 8);
-    ca_tiles_.fb = reinterpret_cast<const double*>(ca_faces_ + ca_face_bytes_ + face_off * 8);
+    ca_faces_ = dev_alloc<char>(plan_.faces_total());
+    ca_tiles_.fa = reinterpret_cast<const double*>(ca_faces_.get() + plan_.face_at(0));
+    ca_tiles_.fb = reinterpret_cast<const double*>(ca_faces_.get() + plan_.face_at(1));
     ca_tiles_.gh = ca_gh_;
     ca_build_faces(ca_geom_, ca_tables_, const_cast<double*>(ca_tiles_.fa), const_cast<double*>(ca_tiles_.fb), ca_gh_, nullptr);
     const bool split = opt_.ca_split == -1 ? geom_.nb != 0 : opt_.ca_split == 1;  // see GpuOptions::ca_split
     if (!split) ca_tiles_.split = 0;
-    ca_tiles_.dma = elem_ == 8 ? (opt_.ca_dma == -1 ? int(split) : opt_.ca_dma) : 0;  // LDS-DMA rows: fp64
+    ca_tiles_.dma = elem == 8 ? (opt_.ca_dma == -1 ? int(split) : opt_.ca_dma) : 0;  // LDS-DMA rows: fp64
     if (ca_tiles_.split && opt_.ca_frame_stream) {
-      HIP_CHECK(hipStreamCreateWithFlags(&ca_side_, hipStreamNonBlocking));
-      HIP_CHECK(hipEventCreateWithFlags(&ca_ev_fork_, hipEventDisableTiming));
-      HIP_CHECK(hipEventCreateWithFlags(&ca_ev_join_, hipEventDisableTiming));
+      ca_side_ = make_stream();
+      ca_ev_fork_ = make_event(hipEventDisableTiming);
+      ca_ev_join_ = make_event(hipEventDisableTiming);
     }
-    HIP_CHECK(hipMalloc(&ca_tbl_, size_t(ca_tiles_.tiles_j) * ca_tiles_.cwords * sizeof(unsigned)));
-    ca_tiles_.tbl = ca_tbl_;
-    ca_build_classes(ca_geom_, ca_tables_, ca_tiles_, ca_tbl_, nullptr);
+    ca_tbl_ = dev_alloc<unsigned>(size_t(ca_tiles_.tiles_j) * ca_tiles_.cwords * sizeof(unsigned));
+    ca_tiles_.tbl = ca_tbl_.get();
+    ca_build_classes(ca_geom_, ca_tables_, ca_tiles_, ca_tbl_.get(), nullptr);
     if (ca_tiles_.fuse) {
-      HIP_CHECK(hipMalloc(&ca_tbl_f_, size_t(ca_tiles_.tiles_j_f) * ca_tiles_.cwords * sizeof(unsigned)));
-      ca_tiles_.tbl_f = ca_tbl_f_;
-      ca_build_classes(ca_geom_, ca_tables_, ca_tiles_, ca_tbl_f_, nullptr, true);
+      ca_tbl_f_ = dev_alloc<unsigned>(size_t(ca_tiles_.tiles_j_f) * ca_tiles_.cwords * sizeof(unsigned));
+      ca_tiles_.tbl_f = ca_tbl_f_.get();
+      ca_build_classes(ca_geom_, ca_tables_, ca_tiles_, ca_tbl_f_.get(), nullptr, true);
     }
     HIP_CHECK(hipStreamSynchronize(nullptr));
-    HIP_CHECK(hipMalloc(&ca_state_, sizeof(CaState)));
-    HIP_CHECK(hipMemset(ca_state_, 0, sizeof(CaState)));
-    HIP_CHECK(hipMalloc(&ca_chunk_, size_t(kCaReduceMaxBlocks) * ca_nq(ca_tiles_.s) * sizeof(double)));
+    ca_state_ = dev_alloc<CaState>(sizeof(CaState));
+    HIP_CHECK(hipMemset(ca_state_.get(), 0, sizeof(CaState)));
+    ca_chunk_ = dev_alloc<double>(size_t(kCaReduceMaxBlocks) * ca_nq(ca_tiles_.s) * sizeof(double));
   }
   init_tiles_ = make_tiles(G, 256, 0);
   // partials: 5 doubles per slot (the s-step Gram partials take ca_nq per tile)
@@ -504,27 +500,26 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
   const size_t npart = size_t(std::max({tiles_.ntiles(), tiles_b_.ntiles(), init_tiles_.ntiles(),
                                         pcg1_ ? std::max(tiles1_.ntiles(), tiles1w_.ntiles()) : 0, ca_slots}));
   npart_ = npart;
-  HIP_CHECK(hipMalloc(&partials_, (npart * 5 + kReduceWsDoubles) * sizeof(double)));
-  reduce_ws_ = partials_ + npart * 5;
+  partials_ = dev_alloc<double>((npart * 5 + kReduceWsDoubles) * sizeof(double));
+  reduce_ws_ = partials_.get() + npart * 5;
   HIP_CHECK(hipMemset(reduce_ws_, 0, kReduceWsDoubles * sizeof(double)));
 
-  layout_ = comm_layout(sd, opt.dtype, pcg1_ || ca_, ca_ && sd.grid.size() > 1 ? gh_ : 0);
+  layout_ = comm_layout(sd, opt.dtype, pcg1_ || ca_, ca_ && sd.grid.size() > 1 ? gh : 0);
   if (external_arena) {
     arena_ = reinterpret_cast<char*>(external_arena);
-    own_arena_ = false;
     PMX_CHECK(external_arena % 256 == 0, "external comm arena must be 256-B aligned");
   } else {
-    HIP_CHECK(hipMalloc(&arena_, layout_.bytes));
-    own_arena_ = true;
+    arena_own_ = dev_alloc<char>(layout_.bytes);
+    arena_ = arena_own_.get();
   }
   HIP_CHECK(hipMemset(arena_, 0, layout_.bytes));
   state_ = reinterpret_cast<PcgState*>(arena_ + layout_.state_off);
-  HIP_CHECK(hipHostMalloc(&host_state_, 2 * sizeof(PcgState), hipHostMallocDefault));
+  host_state_ = host_alloc<PcgState>(2 * sizeof(PcgState), hipHostMallocDefault);
   if (opt_.progress) {
-    HIP_CHECK(hipHostMalloc(&progress_host_, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(progress_host_, 0, 64);
+    progress_host_ = host_alloc<long long>(64, hipHostMallocMapped | hipHostMallocCoherent);
+    std::memset(progress_host_.get(), 0, 64);
     void* d = nullptr;
-    HIP_CHECK(hipHostGetDevicePointer(&d, progress_host_, 0));
+    HIP_CHECK(hipHostGetDevicePointer(&d, progress_host_.get(), 0));
     progress_dev_ = static_cast<long long*>(d);
   }
   if (pcg1_ || ca_) place_fields();
@@ -581,10 +576,17 @@ void GpuSubdomainSolver::probe_iterations(hipStream_t s, hipEvent_t e0, hipEvent
 
 void GpuSubdomainSolver::place_fields() {
   const int K = opt_.placement;
-  const size_t block = 5 * field_stride_;
-  if (K <= 1 || !own_arena_ || block < (size_t(256) << 20)) return;  // small grids: latency-bound
+  const size_t block = plan_.fields_total();
+  if (K <= 1 || !arena_own_ || block < (size_t(256) << 20)) return;  // small grids: latency-bound
   const double t0 = now_s();
-  std::vector<char*> cand{fields_};
+  // candidate blocks; fields_ holds candidate `cur`, whose slot is empty meanwhile
+  std::vector<DevPtr<char>> cand(1);
+  size_t cur = 0;
+  auto use = [&](size_t c) {
+    cand[cur] = std::move(fields_);
+    fields_ = std::move(cand[c]);
+    cur = c;
+  };
   size_t free0 = 0, total_b = 0;
   HIP_CHECK(hipMemGetInfo(&free0, &total_b));
   const size_t keep = std::max(size_t(double(free0) * std::clamp(opt_.placement_keep_free, 0.0, 1.0)),
@@ -598,7 +600,7 @@ void GpuSubdomainSolver::place_fields() {
       (void)hipGetLastError();
       break;
     }
-    cand.push_back(p);
+    cand.emplace_back(p);
   }
   if (cand.size() == 1) {
     placement_s_ = now_s() - t0;
@@ -607,63 +609,53 @@ void GpuSubdomainSolver::place_fields() {
   // the time budget bounds the timed sweeps; allocation (the driver clears reused VRAM) is reported
   // in placement_seconds but not charged to it
   const double t_probe = now_s();
-  auto keep_only = [&](size_t keep) {  // free every other candidate, point the fields at `keep`
-    for (size_t c = 0; c < cand.size(); ++c)
-      if (c != keep) (void)hipFree(cand[c]);
-    fields_ = cand[keep];
-    r2_ = field_raw(4);
-  };
-  hipStream_t s = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const Stream s = make_stream();
+  const Event e0 = make_event(), e1 = make_event();
   try {
-    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
     placement_ms_.clear();
     for (size_t c = 0; c < cand.size(); ++c) {
       if (c > 0 && now_s() - t_probe > opt_.placement_budget_s) break;  // time budget: the rest stay untimed
       placement_ms_.push_back(0.f);
-      fields_ = cand[c];
-      r2_ = field_raw(4);
-      probe_iterations(s, e0, e1);
-      HIP_CHECK(hipEventSynchronize(e1));
-      HIP_CHECK(hipEventElapsedTime(&placement_ms_[c], e0, e1));
+      use(c);
+      probe_iterations(s.get(), e0.get(), e1.get());
+      HIP_CHECK(hipEventSynchronize(e1.get()));
+      HIP_CHECK(hipEventElapsedTime(&placement_ms_[c], e0.get(), e1.get()));
     }
-  } catch (...) {  // keep the first block (the solver's own), release the candidates, then report
-    if (s) (void)hipStreamSynchronize(s);
-    keep_only(0);
+  } catch (...) {  // keep the first block (the solver's own), then report; `cand` frees the others
+    (void)hipStreamSynchronize(s.get());
+    use(0);
     placement_ms_.clear();
     throw;
   }
   const auto pick = opt_.placement_pick == 1 ? std::max_element(placement_ms_.begin(), placement_ms_.end())
                                              : std::min_element(placement_ms_.begin(), placement_ms_.end());
-  keep_only(size_t(pick - placement_ms_.begin()));
-  HIP_CHECK(hipEventDestroy(e0));
-  HIP_CHECK(hipEventDestroy(e1));
-  HIP_CHECK(hipStreamDestroy(s));
+  use(size_t(pick - placement_ms_.begin()));
+  cand.clear();  // the other candidates
   placement_s_ = now_s() - t0;
 }
 
 void GpuSubdomainSolver::progress(long long out[3]) const {
   for (int q = 0; q < 3; ++q)
-    out[q] = progress_host_ ? __atomic_load_n(progress_host_ + q, __ATOMIC_RELAXED) : -1;
+    out[q] = progress_host_ ? __atomic_load_n(progress_host_.get() + q, __ATOMIC_RELAXED) : -1;
 }
 
-int GpuSubdomainSolver::pending_w(const PcgState& st, const void* pp[2], double a[2]) const {
-  int npend = 0;
+// Paired w updates (k_pcg_b_rows): an odd iteration leaves w^{k+1} = w^k + alpha_k p^k pending in device
+// memory.  pcg1 (k_pcg1) leaves w_pend_n (1 or 2) steps pending, p^j in p[j & 1], alpha_j in alpha1[j & 3].
+GpuSubdomainSolver::PendingW GpuSubdomainSolver::pending_w(const PcgState& st) const {
+  PendingW pw;
   if (pcg1_ && st.w_pend_n > 0 && st.w_pend > 0) {
-    npend = st.w_pend_n;
-    for (int q = 0; q < npend; ++q) {
-      const long long j = st.w_pend - (npend - 1) + q;
-      pp[q] = field_base((j & 1) ? 3 : 2);
-      a[q] = st.alpha1[j & 3];
+    pw.n = st.w_pend_n;
+    for (int q = 0; q < pw.n; ++q) {  // q = 0: the oldest pending step
+      const long long j = st.w_pend - (pw.n - 1) + q;
+      pw.field[q] = (j & 1) ? 3 : 2;
+      pw.a[q] = st.alpha1[j & 3];
     }
   } else if (!pcg1_ && st.w_pend > 0) {
-    npend = 1;
-    pp[0] = field_base((st.w_pend & 1) ? 3 : 2);
-    a[0] = st.alpha[st.w_pend & 1];
+    pw.n = 1;
+    pw.field[0] = (st.w_pend & 1) ? 3 : 2;
+    pw.a[0] = st.alpha[st.w_pend & 1];
   }
-  return npend;
+  return pw;
 }
 
 namespace {
@@ -685,8 +677,8 @@ std::vector<char> round_to_storage(const double* v, size_t rows, size_t cols, si
 
 void GpuSubdomainSolver::set_init_data(const double* f, const double* w0, int64_t ld_f, int64_t ld_w0) {
   const size_t nx = size_t(sd_.nx), ny = size_t(sd_.ny);
-  stage_f_ = f ? round_to_storage(f, nx, ny, ld_f ? size_t(ld_f) : ny, elem_) : std::vector<char>();
-  stage_w_ = w0 ? round_to_storage(w0, nx + 2, ny + 2, ld_w0 ? size_t(ld_w0) : ny + 2, elem_) : std::vector<char>();
+  stage_f_ = f ? round_to_storage(f, nx, ny, ld_f ? size_t(ld_f) : ny, plan_.elem) : std::vector<char>();
+  stage_w_ = w0 ? round_to_storage(w0, nx + 2, ny + 2, ld_w0 ? size_t(ld_w0) : ny + 2, plan_.elem) : std::vector<char>();
   dev_f_ = dev_w_ = nullptr;  // each call replaces the data of the next init
 }
 
@@ -705,60 +697,43 @@ void GpuSubdomainSolver::set_init_data_device(const double* f, const double* w0,
   }
 }
 
-template <typename T>
-static void residual_launch(const DevGeom& G, const DevTables& Tb, const void* w, const void* f, int64_t fpitch,
-                            const void* const pp[2], const double a[2], int npend, double* part,
-                            const TileCfg& tc, double sigma, hipStream_t s) {
-  InitData<T> X;
-  // f is nx x ny with row stride fpitch: element (i, j), i, j >= 1, at f[(i - 1) * fpitch + (j - 1)]
-  X.f = f ? static_cast<const T*>(f) - (fpitch + 1) : nullptr;
-  X.fpitch = fpitch;
-  X.pa = static_cast<const T*>(pp[0]);
-  X.pb = static_cast<const T*>(pp[1]);
-  X.ca = a[0];
-  X.cb = a[1];
-  X.npend = npend;
-  X.sigma = sigma;
-  launch_init_data<T>(G, Tb, const_cast<T*>(static_cast<const T*>(w)), nullptr, HaloBufs<T>{}, part, tc, X, true, s);
-}
-
 double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_t ld_f, bool f_on_device) const {
   HIP_CHECK(hipSetDevice(opt_.device));
   PMX_CHECK(!(f && f_on_device) || ld_f >= sd_.ny, "a device right-hand side needs its row stride");
-  const PcgState st = read_state(s);
-  const void* pp[2] = {nullptr, nullptr};
-  double a[2] = {0.0, 0.0};
-  const int npend = pending_w(st, pp, a);
+  const PendingW pw = pending_w(read_state(s));
   // temporary device memory for the call: one partial pair per init tile, and f in the storage type
   // (a device f in fp64 storage is read where it lies)
-  const size_t nt = size_t(init_tiles_.ntiles());
-  const bool host_f = f && !f_on_device, in_place = f && f_on_device && elem_ == 8;
+  const size_t nt = size_t(init_tiles_.ntiles()), elem = plan_.elem;
+  const bool host_f = f && !f_on_device, in_place = f && f_on_device && elem == 8;
   const std::vector<char> hf =
-      host_f ? round_to_storage(f, size_t(sd_.nx), size_t(sd_.ny), ld_f ? size_t(ld_f) : size_t(sd_.ny), elem_)
+      host_f ? round_to_storage(f, size_t(sd_.nx), size_t(sd_.ny), ld_f ? size_t(ld_f) : size_t(sd_.ny), elem)
              : std::vector<char>();
-  const size_t fbytes = f && !in_place ? size_t(sd_.nx) * size_t(sd_.ny) * elem_ : 0;
-  char* tmp = nullptr;
-  HIP_CHECK(hipMalloc(&tmp, 2 * nt * sizeof(double) + fbytes));
-  double* part = reinterpret_cast<double*>(tmp);
-  const void* df = !f ? nullptr : in_place ? static_cast<const void*>(f) : tmp + 2 * nt * sizeof(double);
+  const size_t fbytes = f && !in_place ? size_t(sd_.nx) * size_t(sd_.ny) * elem : 0;
+  const DevPtr<char> tmp = dev_alloc<char>(2 * nt * sizeof(double) + fbytes);
+  double* part = reinterpret_cast<double*>(tmp.get());
+  char* tmp_f = tmp.get() + 2 * nt * sizeof(double);
+  const void* df = !f ? nullptr : in_place ? static_cast<const void*>(f) : tmp_f;
   const int64_t fpitch = in_place ? ld_f : sd_.ny;
   std::vector<double> h(2 * nt);
-  try {
-    if (host_f) HIP_CHECK(hipMemcpyAsync(tmp + 2 * nt * sizeof(double), hf.data(), hf.size(), hipMemcpyHostToDevice, s));
-    if (f && f_on_device && !in_place)
-      launch_scatter<float>(f, ld_f, reinterpret_cast<float*>(tmp + 2 * nt * sizeof(double)), sd_.ny, sd_.nx, sd_.ny, s);
-    if (elem_ == 8)
-      residual_launch<double>(geom_, tables_, field_base(0), df, fpitch, pp, a, npend, part, init_tiles_, spec_.sigma, s);
-    else
-      residual_launch<float>(geom_, tables_, field_base(0), df, fpitch, pp, a, npend, part, init_tiles_, spec_.sigma, s);
-    HIP_CHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(tmp);
-    throw;
-  }
-  HIP_CHECK(hipFree(tmp));
+  if (host_f) HIP_CHECK(hipMemcpyAsync(tmp_f, hf.data(), hf.size(), hipMemcpyHostToDevice, s));
+  if (f && f_on_device && !in_place)
+    launch_scatter<float>(f, ld_f, reinterpret_cast<float*>(tmp_f), sd_.ny, sd_.nx, sd_.ny, s);
+  with_storage([&](auto t) {
+    using T = decltype(t);
+    InitData<T> X;
+    // f is nx x ny with row stride fpitch: element (i, j), i, j >= 1, at f[(i - 1) * fpitch + (j - 1)]
+    X.f = df ? static_cast<const T*>(df) - (fpitch + 1) : nullptr;
+    X.fpitch = fpitch;
+    X.pa = pending_p<T>(pw, 0);
+    X.pb = pending_p<T>(pw, 1);
+    X.ca = pw.a[0];
+    X.cb = pw.a[1];
+    X.npend = pw.n;
+    X.sigma = spec_.sigma;
+    launch_init_data<T>(geom_, tables_, fields<T>().w, nullptr, HaloBufs<T>{}, part, init_tiles_, X, true, s);
+  });
+  HIP_CHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
   double sum = 0.0;
   for (size_t t = 0; t < nt; ++t) sum += h[2 * t + 1];  // tile order: deterministic
   return sum;
@@ -766,27 +741,17 @@ double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_
 
 ErrorStats GpuSubdomainSolver::error_norms(hipStream_t s) const {
   HIP_CHECK(hipSetDevice(opt_.device));
-  const PcgState st = read_state(s);
-  // pending w steps, exactly as download_w applies them
-  const void* pp[2] = {nullptr, nullptr};
-  double a[2] = {0.0, 0.0};
-  const int npend = pending_w(st, pp, a);
+  const PendingW pw = pending_w(read_state(s));  // pending w steps, exactly as download_w applies them
   constexpr int kMaxBlocks = 1024;
-  double* d_out = nullptr;
-  HIP_CHECK(hipMalloc(&d_out, 3 * kMaxBlocks * sizeof(double)));
-  int nb = 0;
-  if (elem_ == 8)
-    nb = launch_error_norms<double>(geom_, tables_, static_cast<const double*>(field_base(0)),
-                                    static_cast<const double*>(pp[0]), a[0], static_cast<const double*>(pp[1]),
-                                    a[1], npend, d_out, kMaxBlocks, s);
-  else
-    nb = launch_error_norms<float>(geom_, tables_, static_cast<const float*>(field_base(0)),
-                                   static_cast<const float*>(pp[0]), a[0], static_cast<const float*>(pp[1]),
-                                   a[1], npend, d_out, kMaxBlocks, s);
+  const DevPtr<double> d_out = dev_alloc<double>(3 * kMaxBlocks * sizeof(double));
+  const int nb = with_storage([&](auto t) {
+    using T = decltype(t);
+    return launch_error_norms<T>(geom_, tables_, fields<T>().w, pending_p<T>(pw, 0), pw.a[0], pending_p<T>(pw, 1),
+                                 pw.a[1], pw.n, d_out.get(), kMaxBlocks, s);
+  });
   std::vector<double> h(3 * size_t(nb));
-  HIP_CHECK(hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(h.data(), d_out.get(), h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  HIP_CHECK(hipFree(d_out));
   ErrorStats e;
   e.max_w = -HUGE_VAL;
   for (int b = 0; b < nb; ++b) {  // block order: deterministic
@@ -795,40 +760,6 @@ ErrorStats GpuSubdomainSolver::error_norms(hipStream_t s) const {
     e.max_w = std::max(e.max_w, h[3 * size_t(b) + 2]);
   }
   return e;
-}
-
-void GpuSubdomainSolver::release() noexcept {
-  (void)hipSetDevice(opt_.device);
-  (void)hipDeviceSynchronize();
-  if (fields_) (void)hipFree(fields_);
-  if (tile_order_) (void)hipFree(tile_order_);
-  if (tile_order_w_) (void)hipFree(tile_order_w_);
-  if (ca_tbl_) (void)hipFree(ca_tbl_);
-  if (ca_tbl_f_) (void)hipFree(ca_tbl_f_);
-  ca_tbl_f_ = nullptr;
-  if (ca_faces_) (void)hipFree(ca_faces_);
-  if (ca_side_) (void)hipStreamDestroy(ca_side_);
-  if (ca_ev_fork_) (void)hipEventDestroy(ca_ev_fork_);
-  if (ca_ev_join_) (void)hipEventDestroy(ca_ev_join_);
-  ca_side_ = nullptr;
-  ca_ev_fork_ = ca_ev_join_ = nullptr;
-  ca_faces_ = nullptr;
-  if (ca_state_) (void)hipFree(ca_state_);
-  if (ca_chunk_) (void)hipFree(ca_chunk_);
-  ca_tbl_ = nullptr;
-  ca_state_ = nullptr;
-  ca_chunk_ = nullptr;
-  if (tables_buf_) (void)hipFree(tables_buf_);
-  if (partials_) (void)hipFree(partials_);
-  if (own_arena_ && arena_) (void)hipFree(arena_);
-  if (host_state_) (void)hipHostFree(host_state_);
-  if (progress_host_) (void)hipHostFree(progress_host_);
-  progress_host_ = progress_dev_ = nullptr;
-  fields_ = r2_ = nullptr;
-  arena_ = nullptr;
-  tables_buf_ = partials_ = nullptr;
-  tile_order_ = tile_order_w_ = nullptr;
-  host_state_ = nullptr;
 }
 
 GpuSubdomainSolver::~GpuSubdomainSolver() {
@@ -849,48 +780,31 @@ GpuSubdomainSolver::~GpuSubdomainSolver() {
     (void)hipFree(wtrace_);
   }
 #endif
-  release();
-}
-
-size_t GpuSubdomainSolver::estimate_device_bytes(const ProblemSpec& spec, const Subdomain& sd,
-                                                 DType dtype, bool single_pass) {
-  const size_t elem = dtype == DType::kFp64 ? 8 : 4, align = 256 / elem;
-  const size_t pitch = round_up(size_t(sd.ny + 2 + 8), align);
-  const size_t field = round_up((align - 1 + size_t(sd.nx + 4) * pitch) * elem, 256);
-  const size_t tables = (4 * size_t(spec.M + 2) + 4 * size_t(spec.N + 2)) * 8 + 8 * size_t(spec.M + 2) * 4;
-  // partials: at most one per 2 rows x 64 columns tile (the smallest auto tile), 5 doubles each
-  const size_t partials = (size_t(sd.nx + 1) / 2 + 1) * (size_t(sd.ny) / 64 + 1) * 40;
-  return (single_pass ? 5 : 4) * field + tables + partials + comm_layout(sd, dtype, single_pass).bytes +
-         (1u << 20);
+  // the device idle, then the members' owners free everything (an external arena is not owned)
+  (void)hipSetDevice(opt_.device);
+  (void)hipDeviceSynchronize();
 }
 
 size_t GpuSubdomainSolver::estimate_device_bytes_algo(const ProblemSpec& spec, const Subdomain& sd, DType dtype,
                                                       int algo) {
-  if (algo != 3) return estimate_device_bytes(spec, sd, dtype, algo == 1);
-  // s-step: w, two (z, p) sets and the two face fields, rows -gh+1 .. nx+gh (gh = 2s = 6 on strips: the
-  // fused pass)
-  const size_t elem = dtype == DType::kFp64 ? 8 : 4, align = 256 / elem;
-  const int gh = sd.grid.size() > 1 ? 2 * kCaMaxS : 2;
-  const size_t pitch = round_up(size_t(sd.ny + 2 + 8 + (sd.grid.Py > 1 ? 2 * gh + 8 : 0)), align);
-  const size_t field = round_up((align - 1 + size_t(sd.nx + 2 * gh) * pitch) * elem, 256);
-  const size_t face = round_up((31 + size_t(sd.nx + 2 * gh) * pitch) * 8, 256);
-  const size_t tables = (4 * size_t(spec.M + 2) + 4 * size_t(spec.N + 2)) * 8 + 8 * size_t(spec.M + 2) * 4;
-  // partials: 21 doubles per 8-row tile of 116 columns (the smallest tiling), row-class words
-  const size_t partials = (size_t(sd.nx) / 8 + 1) * (size_t(sd.ny) / 116 + 1) * 21 * 8 * 2;
-  return 5 * field + 2 * face + tables + partials +
-         comm_layout(sd, dtype, true, sd.grid.size() > 1 ? gh : 0).bytes + (1u << 20);
+  // s-step on decomposed grids: the most ghost rows a solver may choose (2s = 6: the fused pass)
+  const int gh = algo == 3 && sd.grid.size() > 1 ? 2 * kCaMaxS : 2;
+  const MemoryPlan plan(spec, sd, dtype, algo, gh);
+  // partials: at most one per 2 rows x 64 columns tile (the smallest auto tile), 5 doubles each; the
+  // s-step: 21 doubles per 8-row tile of 116 columns (the smallest tiling), row-class words
+  const size_t partials = algo == 3 ? (size_t(sd.nx) / 8 + 1) * (size_t(sd.ny) / 116 + 1) * 21 * 8 * 2
+                                    : (size_t(sd.nx + 1) / 2 + 1) * (size_t(sd.ny) / 64 + 1) * 40;
+  return plan.total() + partials + comm_layout(sd, dtype, algo == 1 || algo == 3, algo == 3 && sd.grid.size() > 1 ? gh : 0).bytes +
+         (1u << 20);
 }
 
 size_t GpuSubdomainSolver::device_bytes() const {
-  const size_t tables = (4 * size_t(spec_.M + 2) + 4 * size_t(spec_.N + 2)) * sizeof(double) +
-                        8 * size_t(spec_.M + 2) * sizeof(int);
-  return (r2_ ? 5 : 4) * field_stride_ + tables + (npart_ * 5 + kReduceWsDoubles) * sizeof(double) +
-         (own_arena_ ? layout_.bytes : 0) + (ca_faces_ ? 2 * ca_face_bytes_ : 0);
+  return plan_.total() + (npart_ * 5 + kReduceWsDoubles) * sizeof(double) + (arena_own_ ? layout_.bytes : 0);
 }
 
 void* GpuSubdomainSolver::field_base(int which) const {
   PMX_CHECK(which >= 0 && which < 4, "field index");
-  return field_raw(which) + field_off_ * elem_;
+  return field_ptr(which);
 }
 
 template <typename T>
@@ -912,10 +826,9 @@ void GpuSubdomainSolver::after_launch(hipStream_t s) const {
 
 template <typename T>
 void GpuSubdomainSolver::init_impl(hipStream_t s) {
-  for (int f = 0; f < 4; ++f) HIP_CHECK(hipMemsetAsync(field_raw(f), 0, field_bytes_, s));
-  if (r2_) HIP_CHECK(hipMemsetAsync(r2_, 0, field_bytes_, s));
+  for (int f = 0; f < plan_.nfields; ++f) HIP_CHECK(hipMemsetAsync(field_raw(f), 0, plan_.field_bytes, s));
   HIP_CHECK(hipMemsetAsync(arena_, 0, layout_.bytes, s));
-  PcgState& st = host_state_[1];  // template (never rewritten while a copy is in flight)
+  PcgState& st = host_state_.get()[1];  // template (never rewritten while a copy is in flight)
   std::memset(&st, 0, sizeof(st));
   st.delta = spec_.delta;
   st.bd_tol = spec_.breakdown_tol;
@@ -929,7 +842,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
   // recovered p^{k-2} carries the STORAGE rounding of p^{k-1} and r^{k-1} times 1 / beta_{k-1}: with fp32
   // fields w then misses the oracle by 2.7e-6 max|w| where re-reading p^{k-2} gives 7e-8 (measured, 40x40
   // and 97x130, constant rhs).  There the sweep re-reads below beta = 0.5 (growth <= 3 roundings).
-  if (spec_.sigma != 0.0 && elem_ == 4 && opt_.pair_w != 2) st.pair_min_beta = 0.5;
+  if (spec_.sigma != 0.0 && sizeof(T) == 4 && opt_.pair_w != 2) st.pair_min_beta = 0.5;
   st.w_cycle = w_cycle();
   // stop rule: the step rule leaves PcgState's tail zero, as every build before it did
   stop_ref_data_ = false;
@@ -942,11 +855,11 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
   }
   host_k_ = st.it;
   if (progress_host_) {  // the device has finished with them: init follows a synchronised state
-    for (int q = 0; q < 3; ++q) __atomic_store_n(progress_host_ + q, 0LL, __ATOMIC_RELAXED);
+    for (int q = 0; q < 3; ++q) __atomic_store_n(progress_host_.get() + q, 0LL, __ATOMIC_RELAXED);
   }
   HIP_CHECK(hipMemcpyAsync(state_, &st, sizeof(PcgState), hipMemcpyHostToDevice, s));
-  T* w = static_cast<T*>(field_base(0));
-  T* r = static_cast<T*>(field_base(1));
+  const Fields<T> F = fields<T>();
+  T *w = F.w, *r = F.r;
   // k_init packs r^0 into the two-sweep send buffers; pcg1 packs its own radius-2 halo
   DevGeom G = geom_;
   if (pcg1_) G.nb = 0;
@@ -973,7 +886,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     else if (X.has_w)
       HIP_CHECK(hipMemcpy2DAsync(w, P, stage_w_.data(), (ny + 2) * sizeof(T), (ny + 2) * sizeof(T), nx + 2,
                                  hipMemcpyHostToDevice, s));
-    launch_init_data<T>(G, tables_, w, r, halo<T>(), partials_, init_tiles_, X, false, s);
+    launch_init_data<T>(G, tables_, w, r, halo<T>(), partials_.get(), init_tiles_, X, false, s);
     after_launch(s);
     if (X.has_w) {
       HIP_CHECK(hipMemsetAsync(w, 0, (ny + 2) * sizeof(T), s));
@@ -986,50 +899,51 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     std::vector<char>().swap(stage_w_);
     dev_f_ = dev_w_ = nullptr;
   } else {
-    launch_init<T>(G, tables_, w, r, halo<T>(), partials_, init_tiles_, s, spec_.sigma);
+    launch_init<T>(G, tables_, w, r, halo<T>(), partials_.get(), init_tiles_, s, spec_.sigma);
     after_launch(s);
   }
   // red_b[1] = (z^0, r^0); red_b[0] = rho_B = (D^-1 B, B) when the residual rule starts from a w0, else 0
-  launch_reduce(partials_, init_tiles_.ntiles(), 2, stop_ref_data_ ? g_.h1h2 : 0.0, g_.h1h2, state_->red_b, state_, 0,
+  launch_reduce(partials_.get(), init_tiles_.ntiles(), 2, stop_ref_data_ ? g_.h1h2 : 0.0, g_.h1h2, state_->red_b, state_, 0,
                 reduce_ws_, s);
   after_launch(s);
   if (ca_) {  // set 0: z^0 = D^-1 r^0 (in r's buffer), p^0 = z^0; block counter 0
     std::memset(&ca_init_, 0, sizeof(CaState));
     ca_init_.s = ca_tiles_.s;  // (checked by load_checkpoint)
-    HIP_CHECK(hipMemcpyAsync(ca_state_, &ca_init_, sizeof(CaState), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(ca_state_.get(), &ca_init_, sizeof(CaState), hipMemcpyHostToDevice, s));
     ca_blk_ = 0;
     ca_primed_ = false;
-    launch_ca_init<T>(ca_geom_, ca_tables_, static_cast<T*>(field_base(1)), static_cast<T*>(field_base(2)), s);
+    launch_ca_init<T>(ca_geom_, ca_tables_, F.r, F.p0, s);
     after_launch(s);
   }
 }
 
-template <typename T>
-void GpuSubdomainSolver::halo_impl(hipStream_t s, bool unpack) {
-  launch_pcg1_halo<T>(geom_, static_cast<T*>(field_base(1)), reinterpret_cast<T*>(r2_ + field_off_ * elem_),
-                      static_cast<T*>(field_base(2)), static_cast<T*>(field_base(3)), halo<T>(), halo_target_,
-                      unpack, s, progress_dev_);
-  after_launch(s);
-}
-
-// 2-D blocks (no direct rows): pack / unpack the gh edge lines and corners of the set ca_halo_msgs would
-// name (the set the next block reads, CaState::blk & 1 mirrored by ca_blk_) through the arena slots
-void GpuSubdomainSolver::ca_halo_impl(hipStream_t s, bool unpack) {
-  const int set = int(ca_blk_ & 1);
-  char* fz = set ? r2_ + field_off_ * elem_ : static_cast<char*>(field_base(1));
-  char* fp = static_cast<char*>(field_base(set ? 3 : 2));
-  if (elem_ == 8)
-    launch_ca_halo<double>(geom_, reinterpret_cast<double*>(fz), reinterpret_cast<double*>(fp), halo<double>(), gh_,
-                           unpack, s, progress_dev_);
-  else
-    launch_ca_halo<float>(geom_, reinterpret_cast<float*>(fz), reinterpret_cast<float*>(fp), halo<float>(), gh_, unpack,
-                          s, progress_dev_);
+// pcg1: the radius-2 edges of the buffers the next sweep reads.  s-step 2-D blocks (no direct rows): the gh
+// edge lines and corners of the set ca_halo_msgs would name (the set the next block reads, CaState::blk & 1
+// mirrored by ca_blk_).  Both through the arena slots.
+void GpuSubdomainSolver::halo_launch(hipStream_t s, bool unpack) {
+  with_storage([&](auto t) {
+    using T = decltype(t);
+    const Fields<T> F = fields<T>();
+    if (ca_)
+      launch_ca_halo<T>(geom_, (ca_blk_ & 1) ? F.r2 : F.r, (ca_blk_ & 1) ? F.p1 : F.p0, halo<T>(), plan_.gh, unpack, s,
+                        progress_dev_);
+    else
+      launch_pcg1_halo<T>(geom_, F.r, F.r2, F.p0, F.p1, halo<T>(), halo_target_, unpack, s, progress_dev_);
+  });
   after_launch(s);
 }
 
 void GpuSubdomainSolver::set_direct_rows(bool on) {
   PMX_CHECK(!on || can_direct_rows(), "direct-row ghost exchange needs pcg1 on a row strip (x neighbours only)");
   direct_rows_ = on;
+}
+
+// Direct rows: `nrows` rows starting at local row srow of field f go to the neighbour across `slot`, whose
+// rows land at rrow, as ONE span: the first nrows - 1 rows whole (a row's padding ends with column -1 of the
+// next) and the last row's columns 0 .. ny+1; on a row strip the ghost columns are Dirichlet zeros
+HaloMsg GpuSubdomainSolver::row_msg(int slot, int order, int f, int nrows, int64_t srow, int64_t rrow) const {
+  return HaloMsg{slot, order, layout_.peer[slot], int((nrows - 1) * plan_.pitch + sd_.ny + 2),
+                 field_ptr(f, srow), field_ptr(f, rrow)};
 }
 
 HaloMsgs GpuSubdomainSolver::halo_msgs() const {
@@ -1042,97 +956,58 @@ HaloMsgs GpuSubdomainSolver::halo_msgs() const {
   }
   if (ca_) return ca_halo_msgs(int(ca_blk_ & 1));
   // sweep t reads r^{t-1} from (t & 1 ? r2 : r) and p^{t-1} from (t & 1 ? p0 : p1) (k_pcg1)
-  const long long t = halo_target_;
-  char* fr = (t & 1) ? r2_ + field_off_ * elem_ : static_cast<char*>(field_base(1));
-  char* fp = static_cast<char*>(field_base((t & 1) ? 2 : 3));
-  const int64_t P = geom_.pitch;
-  // rows q, q+1 as one span: row q whole (its padding ends with column -1 of row q+1) and row q+1's
-  // columns 0 .. ny+1; on a row strip the ghost columns are Dirichlet zeros on both sides
-  const int count = int(P + sd_.ny + 2);
+  const bool odd = halo_target_ & 1;
   for (int slot = 0; slot < 2; ++slot) {
     if (layout_.peer[slot] < 0) continue;
     const int64_t srow = slot == 0 ? 1 : sd_.nx - 1, rrow = slot == 0 ? -1 : sd_.nx + 1;
-    for (int f = 0; f < 2; ++f) {
-      char* base = f == 0 ? fr : fp;
-      out.m[out.n++] = HaloMsg{slot, f, layout_.peer[slot], count, base + srow * P * int64_t(elem_),
-                               base + rrow * P * int64_t(elem_)};
-    }
+    out.m[out.n++] = row_msg(slot, 0, odd ? 4 : 1, 2, srow, rrow);
+    out.m[out.n++] = row_msg(slot, 1, odd ? 2 : 3, 2, srow, rrow);
   }
   return out;
 }
 
 void GpuSubdomainSolver::enqueue_halo_pack(hipStream_t s) {
-  if (ca_ && geom_.nb != 0 && !direct_rows_) {
-    ca_halo_impl(s, false);
-    return;
-  }
-  if (!pcg1_ || geom_.nb == 0 || direct_rows_) return;
-  if (opt_.dtype == DType::kFp64) halo_impl<double>(s, false); else halo_impl<float>(s, false);
+  if ((pcg1_ || ca_) && geom_.nb != 0 && !direct_rows_) halo_launch(s, false);
 }
 
 void GpuSubdomainSolver::enqueue_halo_unpack(hipStream_t s) {
-  if (ca_ && geom_.nb != 0 && !direct_rows_) {
-    ca_halo_impl(s, true);
-    return;
-  }
-  if (!pcg1_ || geom_.nb == 0 || direct_rows_) return;
-  if (opt_.dtype == DType::kFp64) halo_impl<double>(s, true); else halo_impl<float>(s, true);
+  if ((pcg1_ || ca_) && geom_.nb != 0 && !direct_rows_) halo_launch(s, true);
 }
 
 template <typename T>
-void GpuSubdomainSolver::phase_a_impl(hipStream_t s) {
-  enqueue_kernel_a(s);
-  enqueue_reduce_a(s);
-}
-
-template <typename T>
-void GpuSubdomainSolver::phase_a_kernel_only(hipStream_t s, int part) {
+void GpuSubdomainSolver::kernel_a(hipStream_t s, int part) {
+  const Fields<T> F = fields<T>();
   if constexpr (sizeof(T) == 8) {
     if (block1_) {
       PMX_CHECK(part == 0, "block tiles run whole sweeps (undecomposed grids)");
-      const double h = g_.h1h2, wdiff = spec_.norm == Norm::kWeighted ? g_.h1h2 : 1.0;
-      const double wts[5] = {h, h, h, h, wdiff};
       // the reduce_n ticket (never in flight together with this sweep: same stream)
       unsigned* ticket = block_fused_ ? reinterpret_cast<unsigned*>(reduce_ws_ + kReduceNOffset + 8 * kReduceMaxBlocks)
                                       : nullptr;
-      launch_pcg1_block<T>(geom_, tables_, static_cast<T*>(field_base(0)), static_cast<T*>(field_base(1)),
-                           reinterpret_cast<T*>(r2_ + field_off_ * elem_), static_cast<T*>(field_base(2)),
-                           static_cast<T*>(field_base(3)), partials_, state_, tiles1_for(w_sweep_next()), s,
-                           w_sweep_next(), wts, ticket, progress_dev_);
+      launch_pcg1_block<T>(geom_, tables_, F.w, F.r, F.r2, F.p0, F.p1, partials_.get(), state_,
+                           tiles1_for(w_sweep_next()), s, w_sweep_next(), weights1().v, ticket, progress_dev_);
       return;
     }
   }
   if (pcg1_)
-    launch_pcg1<T>(geom_, tables_, static_cast<T*>(field_base(0)), static_cast<T*>(field_base(1)),
-                   reinterpret_cast<T*>(r2_ + field_off_ * elem_), static_cast<T*>(field_base(2)), static_cast<T*>(field_base(3)), partials_, state_,
-                   tiles1_for(w_sweep_next()), s, part, w_sweep_next(), spec_.sigma);
+    launch_pcg1<T>(geom_, tables_, F.w, F.r, F.r2, F.p0, F.p1, partials_.get(), state_, tiles1_for(w_sweep_next()), s,
+                   part, w_sweep_next(), spec_.sigma);
   else
-    launch_pcg_a_wave<T>(geom_, tables_, static_cast<const T*>(field_base(1)),
-                         static_cast<T*>(field_base(2)), static_cast<T*>(field_base(3)), halo<T>(),
-                         partials_, state_, tiles_, opt_.exact, s);
+    launch_pcg_a_wave<T>(geom_, tables_, F.r, F.p0, F.p1, halo<T>(), partials_.get(), state_, tiles_, opt_.exact, s);
 }
 
 template <typename T>
-void GpuSubdomainSolver::phase_b_impl(hipStream_t s, bool pack) {
-  enqueue_kernel_b(s, pack);
-  enqueue_reduce_b(s);
-}
-
-template <typename T>
-void GpuSubdomainSolver::phase_b_kernel_only(hipStream_t s, bool pack) {
+void GpuSubdomainSolver::kernel_b(hipStream_t s, bool pack) {
   if (pcg1_) return;  // the single sweep ran in phase a
   // pcg_b reads G.nb only to pack the send buffers: clearing it skips the packing
   DevGeom G = geom_;
   if (!pack) G.nb = 0;
-  launch_pcg_b_wave<T>(G, tables_, static_cast<T*>(field_base(0)),
-                       static_cast<T*>(field_base(1)), static_cast<const T*>(field_base(2)),
-                       static_cast<const T*>(field_base(3)), halo<T>(), partials_, state_, tiles_b_,
-                       opt_.exact, s);
+  const Fields<T> F = fields<T>();
+  launch_pcg_b_wave<T>(G, tables_, F.w, F.r, F.p0, F.p1, halo<T>(), partials_.get(), state_, tiles_b_, opt_.exact, s);
 }
 
 void GpuSubdomainSolver::enqueue_init(hipStream_t s) {
   HIP_CHECK(hipSetDevice(opt_.device));
-  if (opt_.dtype == DType::kFp64) init_impl<double>(s); else init_impl<float>(s);
+  with_storage([&](auto t) { init_impl<decltype(t)>(s); });
 }
 void GpuSubdomainSolver::enqueue_stop_init(hipStream_t s) {
   if (spec_.stop != StopRule::kResidual) return;
@@ -1141,18 +1016,20 @@ void GpuSubdomainSolver::enqueue_stop_init(hipStream_t s) {
   after_launch(s);
 }
 void GpuSubdomainSolver::enqueue_phase_a(hipStream_t s) {
-  if (opt_.dtype == DType::kFp64) phase_a_impl<double>(s); else phase_a_impl<float>(s);
+  enqueue_kernel_a(s);
+  enqueue_reduce_a(s);
 }
 void GpuSubdomainSolver::enqueue_phase_b(hipStream_t s, bool pack) {
-  if (opt_.dtype == DType::kFp64) phase_b_impl<double>(s, pack); else phase_b_impl<float>(s, pack);
+  enqueue_kernel_b(s, pack);
+  enqueue_reduce_b(s);
 }
 void GpuSubdomainSolver::enqueue_kernel_a(hipStream_t s) {
-  if (opt_.dtype == DType::kFp64) phase_a_kernel_only<double>(s); else phase_a_kernel_only<float>(s);
+  with_storage([&](auto t) { kernel_a<decltype(t)>(s); });
   after_launch(s);
 }
 void GpuSubdomainSolver::enqueue_kernel_a_part(hipStream_t s, int part) {
   PMX_CHECK(pcg1_, "interior/frame sweeps are a pcg1 feature");
-  if (opt_.dtype == DType::kFp64) phase_a_kernel_only<double>(s, part); else phase_a_kernel_only<float>(s, part);
+  with_storage([&](auto t) { kernel_a<decltype(t)>(s, part); });
   after_launch(s);
 }
 void GpuSubdomainSolver::enqueue_reduce_a(hipStream_t s) {
@@ -1161,45 +1038,33 @@ void GpuSubdomainSolver::enqueue_reduce_a(hipStream_t s) {
     return;
   }
   if (pcg1_) {
-    const double h = g_.h1h2, wdiff = spec_.norm == Norm::kWeighted ? g_.h1h2 : 1.0;
-    const double wts[5] = {h, h, h, h, wdiff};
     // the sweep just enqueued (host_k not bumped yet) wrote one partial per tile of its tiling
-    launch_reduce_n(partials_, tiles1_for(w_sweep_next()).ntiles(), 5, wts, state_->red_c, state_,
-                    kSkipIfDone | kBumpIter,
-                    reduce_ws_, s, progress_dev_);
+    launch_reduce_n(partials_.get(), tiles1_for(w_sweep_next()).ntiles(), 5, weights1().v, state_->red_c, state_,
+                    kSkipIfDone | kBumpIter, reduce_ws_, s, progress_dev_);
     ++host_k_;  // mirrors the S->it bump (see host_k())
     after_launch(s);
     return;
   }
-  launch_reduce(partials_, tiles_.ntiles(), 1, g_.h1h2, 0.0, state_->red_a, state_, kSkipIfDone,
-                reduce_ws_, s);
+  launch_reduce(partials_.get(), tiles_.ntiles(), 1, g_.h1h2, 0.0, state_->red_a, state_, kSkipIfDone, reduce_ws_, s);
   after_launch(s);
 }
 void GpuSubdomainSolver::enqueue_kernel_b(hipStream_t s, bool pack) {
-  if (opt_.dtype == DType::kFp64) phase_b_kernel_only<double>(s, pack);
-  else phase_b_kernel_only<float>(s, pack);
+  with_storage([&](auto t) { kernel_b<decltype(t)>(s, pack); });
   after_launch(s);
 }
 void GpuSubdomainSolver::enqueue_reduce_b(hipStream_t s) {
   if (pcg1_) return;
   const double wdiff = spec_.norm == Norm::kWeighted ? g_.h1h2 : 1.0;
-  launch_reduce(partials_, tiles_b_.ntiles(), 2, wdiff, g_.h1h2, state_->red_b, state_,
+  launch_reduce(partials_.get(), tiles_b_.ntiles(), 2, wdiff, g_.h1h2, state_->red_b, state_,
                 kSkipIfDone | kBumpIter, reduce_ws_, s);
   after_launch(s);
-}
-
-template <typename T>
-static void pack_impl(const GpuSubdomainSolver& g, HaloBufs<T> H, hipStream_t s) {
-  launch_edge_r<T>(g.geom(), g.tables(), static_cast<const T*>(g.field_base(1)),
-                   static_cast<const T*>(g.field_base(2)), static_cast<const T*>(g.field_base(3)), H,
-                   g.state_dev(), g.options().exact, s);
 }
 
 void GpuSubdomainSolver::enqueue_poison_recv(hipStream_t s) {
   if (direct_rows_) {  // the ghost rows the next exchange writes
     const HaloMsgs ms = halo_msgs();
     for (int q = 0; q < ms.n; ++q)
-      HIP_CHECK(hipMemsetAsync(ms.m[q].recv, 0xFF, size_t(ms.m[q].count) * elem_, s));
+      HIP_CHECK(hipMemsetAsync(ms.m[q].recv, 0xFF, size_t(ms.m[q].count) * plan_.elem, s));
     return;
   }
   const size_t off = layout_.recv_off[0];
@@ -1229,23 +1094,24 @@ void GpuSubdomainSolver::save_checkpoint(std::ostream& os, hipStream_t s) const 
   std::memcpy(h.magic, kCkptMagic, 8);
   h.version = ckpt_version();
   h.M = spec_.M; h.N = spec_.N; h.gi0 = sd_.gi0(); h.gj0 = sd_.gj0();
-  h.rank = sd_.rank; h.elem = int32_t(elem_); h.norm = int32_t(spec_.norm);
-  h.nx = sd_.nx; h.ny = sd_.ny; h.pitch = geom_.pitch; h.field_bytes = int64_t(field_bytes_);
+  h.rank = sd_.rank; h.elem = int32_t(plan_.elem); h.norm = int32_t(spec_.norm);
+  h.nx = sd_.nx; h.ny = sd_.ny; h.pitch = geom_.pitch; h.field_bytes = int64_t(plan_.field_bytes);
   h.arena_bytes = int64_t(layout_.bytes); h.max_iter = spec_.effective_max_iter(); h.delta = spec_.delta;
   os.write(reinterpret_cast<const char*>(&h), sizeof(h));
-  std::vector<char> buf(std::max(4 * field_bytes_, layout_.bytes));
-  for (int f = 0; f < 4; ++f)
-    HIP_CHECK(hipMemcpy(buf.data() + size_t(f) * field_bytes_, field_raw(f), field_bytes_, hipMemcpyDeviceToHost));
-  os.write(buf.data(), std::streamsize(4 * field_bytes_));
+  // file order: fields 0 .. 3, the arena, then field 4 (r2 / the second z buffer) where there is one
+  const size_t fb = plan_.field_bytes;
+  std::vector<char> buf(std::max(4 * fb, layout_.bytes));
+  HIP_CHECK(hipMemcpy(buf.data(), field_raw(0), 4 * fb, hipMemcpyDeviceToHost));
+  os.write(buf.data(), std::streamsize(4 * fb));
   HIP_CHECK(hipMemcpy(buf.data(), arena_, layout_.bytes, hipMemcpyDeviceToHost));
   os.write(buf.data(), std::streamsize(layout_.bytes));
-  if (pcg1_ || ca_) {
-    HIP_CHECK(hipMemcpy(buf.data(), r2_, field_bytes_, hipMemcpyDeviceToHost));
-    os.write(buf.data(), std::streamsize(field_bytes_));
+  if (plan_.nfields == 5) {
+    HIP_CHECK(hipMemcpy(buf.data(), field_raw(4), fb, hipMemcpyDeviceToHost));
+    os.write(buf.data(), std::streamsize(fb));
   }
   if (ca_) {
     CaState c{};
-    HIP_CHECK(hipMemcpy(&c, ca_state_, sizeof(CaState), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&c, ca_state_.get(), sizeof(CaState), hipMemcpyDeviceToHost));
     PMX_CHECK(c.pend_n == 0 && c.nupd <= 0, "s-step checkpoint inside a batch (a block's stop test is pending)");
     os.write(reinterpret_cast<const char*>(&c), sizeof(c));
     // a carried fused schedule: the next block's Gram partials (so a resume continues bitwise)
@@ -1253,7 +1119,7 @@ void GpuSubdomainSolver::save_checkpoint(std::ostream& os, hipStream_t s) const 
     os.write(reinterpret_cast<const char*>(&primed), sizeof(primed));
     if (primed) {
       std::vector<double> part(ca_primed_doubles());
-      HIP_CHECK(hipMemcpy(part.data(), partials_, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(part.data(), partials_.get(), part.size() * sizeof(double), hipMemcpyDeviceToHost));
       os.write(reinterpret_cast<const char*>(part.data()), std::streamsize(part.size() * sizeof(double)));
     }
   }
@@ -1271,18 +1137,18 @@ void GpuSubdomainSolver::load_checkpoint(std::istream& is, hipStream_t s) {
                 h.nx == sd_.nx && h.ny == sd_.ny && h.rank == sd_.rank,
             "checkpoint is for a different grid/decomposition (M=" << h.M << " N=" << h.N << " rank "
                                                                   << h.rank << ")");
-  PMX_CHECK(h.elem == int32_t(elem_) && h.pitch == geom_.pitch &&
-                h.field_bytes == int64_t(field_bytes_) && h.arena_bytes == int64_t(layout_.bytes),
+  const size_t fb = plan_.field_bytes;
+  PMX_CHECK(h.elem == int32_t(plan_.elem) && h.pitch == geom_.pitch && h.field_bytes == int64_t(fb) &&
+                h.arena_bytes == int64_t(layout_.bytes),
             "checkpoint precision/layout differs from this solver");
   PMX_CHECK(h.norm == int32_t(spec_.norm) && h.delta == spec_.delta &&
                 h.max_iter == spec_.effective_max_iter(),
             "checkpoint was written with a different stop rule (norm/delta/max_iter)");
-  std::vector<char> buf(std::max(4 * field_bytes_, layout_.bytes));
-  is.read(buf.data(), std::streamsize(4 * field_bytes_));
+  std::vector<char> buf(std::max(4 * fb, layout_.bytes));
+  is.read(buf.data(), std::streamsize(4 * fb));
   PMX_CHECK(is.good(), "truncated checkpoint (fields)");
   HIP_CHECK(hipStreamSynchronize(s));
-  for (int f = 0; f < 4; ++f)
-    HIP_CHECK(hipMemcpy(field_raw(f), buf.data() + size_t(f) * field_bytes_, field_bytes_, hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(field_raw(0), buf.data(), 4 * fb, hipMemcpyHostToDevice));
   is.read(buf.data(), std::streamsize(layout_.bytes));
   PMX_CHECK(is.good(), "truncated checkpoint (scalars/halos)");
   PcgState ck{};
@@ -1302,10 +1168,10 @@ void GpuSubdomainSolver::load_checkpoint(std::istream& is, hipStream_t s) {
   }
   HIP_CHECK(hipMemcpy(arena_, buf.data(), layout_.bytes, hipMemcpyHostToDevice));
   host_k_ = ck.it;
-  if (pcg1_ || ca_) {
-    is.read(buf.data(), std::streamsize(field_bytes_));
+  if (plan_.nfields == 5) {
+    is.read(buf.data(), std::streamsize(fb));
     PMX_CHECK(is.good(), "truncated checkpoint (r2 / second z buffer)");
-    HIP_CHECK(hipMemcpy(r2_, buf.data(), field_bytes_, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(field_raw(4), buf.data(), fb, hipMemcpyHostToDevice));
   }
   if (ca_) {
     CaState c{};
@@ -1313,7 +1179,7 @@ void GpuSubdomainSolver::load_checkpoint(std::istream& is, hipStream_t s) {
     PMX_CHECK(is.good(), "truncated checkpoint (s-step state)");
     PMX_CHECK(c.s == ca_tiles_.s, "checkpoint was written with s = " << c.s << ", this solver runs s = " << ca_tiles_.s);
     c.ticket = 0u;
-    HIP_CHECK(hipMemcpy(ca_state_, &c, sizeof(CaState), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(ca_state_.get(), &c, sizeof(CaState), hipMemcpyHostToDevice));
     ca_blk_ = c.blk;  // the (z, p) set the next block reads
     int32_t primed = 0;
     is.read(reinterpret_cast<char*>(&primed), sizeof(primed));
@@ -1322,7 +1188,7 @@ void GpuSubdomainSolver::load_checkpoint(std::istream& is, hipStream_t s) {
       std::vector<double> part(ca_primed_doubles());
       is.read(reinterpret_cast<char*>(part.data()), std::streamsize(part.size() * sizeof(double)));
       PMX_CHECK(is.good(), "truncated checkpoint (carried Gram partials)");
-      HIP_CHECK(hipMemcpy(partials_, part.data(), part.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(partials_.get(), part.data(), part.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     ca_primed_ = primed != 0;
   }
@@ -1330,15 +1196,18 @@ void GpuSubdomainSolver::load_checkpoint(std::istream& is, hipStream_t s) {
 
 void GpuSubdomainSolver::enqueue_pack(hipStream_t s) {
   if (geom_.nb == 0 || pcg1_) return;
-  if (opt_.dtype == DType::kFp64) pack_impl<double>(*this, halo<double>(), s);
-  else pack_impl<float>(*this, halo<float>(), s);
+  with_storage([&](auto t) {
+    using T = decltype(t);
+    const Fields<T> F = fields<T>();
+    launch_edge_r<T>(geom_, tables_, F.r, F.p0, F.p1, halo<T>(), state_, opt_.exact, s);
+  });
   after_launch(s);
 }
 
 double GpuSubdomainSolver::bench_kernel(int which, int abl, int reps, hipStream_t s) {
   PMX_CHECK(!ca_, "not available for the s-step solver");
   HIP_CHECK(hipSetDevice(opt_.device));
-  PcgState& st = host_state_[1];
+  PcgState& st = host_state_.get()[1];
   std::memset(&st, 0, sizeof(st));
   st.delta = 0.0;
   // a mid-solve iteration: beta path, p^{k-1} read.  which = 2: pcg_b on an odd iteration (w
@@ -1361,37 +1230,29 @@ double GpuSubdomainSolver::bench_kernel(int which, int abl, int reps, hipStream_
   const TileCfg saved = tiles_, saved_b = tiles_b_;
   tiles_.abl = abl;
   tiles_b_.abl = abl;
-  auto launch = [&]() {
-    HIP_CHECK(hipMemcpyAsync(state_, &st, sizeof(PcgState), hipMemcpyHostToDevice, s));
-    if (which == 0 || pcg1_) {
-      if (opt_.dtype == DType::kFp64) phase_a_kernel_only<double>(s); else phase_a_kernel_only<float>(s);
-    } else {
-      if (opt_.dtype == DType::kFp64) phase_b_kernel_only<double>(s); else phase_b_kernel_only<float>(s);
-    }
+  auto launch = [&] {
+    with_storage([&](auto t) {
+      using T = decltype(t);
+      if (which == 0 || pcg1_) kernel_a<T>(s); else kernel_b<T>(s);
+    });
   };
-  launch();
-  launch();
+  for (int k = 0; k < 2; ++k) {
+    HIP_CHECK(hipMemcpyAsync(state_, &st, sizeof(PcgState), hipMemcpyHostToDevice, s));
+    launch();
+  }
   HIP_CHECK(hipStreamSynchronize(s));
-  hipEvent_t e0, e1;
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
+  const Event e0 = make_event(), e1 = make_event();
   float total = 0.f;
   for (int k = 0; k < reps; ++k) {
     HIP_CHECK(hipMemcpyAsync(state_, &st, sizeof(PcgState), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipEventRecord(e0, s));
-    if (which == 0 || pcg1_) {
-      if (opt_.dtype == DType::kFp64) phase_a_kernel_only<double>(s); else phase_a_kernel_only<float>(s);
-    } else {
-      if (opt_.dtype == DType::kFp64) phase_b_kernel_only<double>(s); else phase_b_kernel_only<float>(s);
-    }
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipEventSynchronize(e1));
+    HIP_CHECK(hipEventRecord(e0.get(), s));
+    launch();
+    HIP_CHECK(hipEventRecord(e1.get(), s));
+    HIP_CHECK(hipEventSynchronize(e1.get()));
     float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    HIP_CHECK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
     total += ms;
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   tiles_ = saved;
   tiles_b_ = saved_b;
   return double(total) / reps;
@@ -1399,15 +1260,15 @@ double GpuSubdomainSolver::bench_kernel(int which, int abl, int reps, hipStream_
 
 PcgState GpuSubdomainSolver::read_state(hipStream_t s) const {
   HIP_CHECK(hipSetDevice(opt_.device));
-  HIP_CHECK(hipMemcpyAsync(&host_state_[0], state_, sizeof(PcgState), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(host_state_.get(), state_, sizeof(PcgState), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  return host_state_[0];
+  return *host_state_;
 }
 
 std::vector<double> GpuSubdomainSolver::read_partials(hipStream_t s) const {
   HIP_CHECK(hipSetDevice(opt_.device));
   std::vector<double> h(npart_ * 5);
-  HIP_CHECK(hipMemcpyAsync(h.data(), partials_, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(h.data(), partials_.get(), h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   return h;
 }
@@ -1415,7 +1276,7 @@ std::vector<double> GpuSubdomainSolver::read_partials(hipStream_t s) const {
 std::vector<double> GpuSubdomainSolver::download_field(int which, hipStream_t s) const {
   HIP_CHECK(hipSetDevice(opt_.device));
   const size_t n = size_t(sd_.nx + 2) * geom_.pitch;
-  std::vector<char> raw(n * elem_);
+  std::vector<char> raw(n * plan_.elem);
   HIP_CHECK(hipMemcpyAsync(raw.data(), field_base(which), raw.size(), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   std::vector<double> out(size_t(sd_.nx + 2) * (sd_.ny + 2));
@@ -1423,7 +1284,7 @@ std::vector<double> GpuSubdomainSolver::download_field(int which, hipStream_t s)
     for (int lj = 0; lj <= sd_.ny + 1; ++lj) {
       const size_t src = size_t(li) * geom_.pitch + lj;
       out[size_t(li) * (sd_.ny + 2) + lj] =
-          elem_ == 8 ? reinterpret_cast<const double*>(raw.data())[src]
+          plan_.elem == 8 ? reinterpret_cast<const double*>(raw.data())[src]
                      : double(reinterpret_cast<const float*>(raw.data())[src]);
     }
   return out;
@@ -1431,32 +1292,17 @@ std::vector<double> GpuSubdomainSolver::download_field(int which, hipStream_t s)
 
 std::vector<double> GpuSubdomainSolver::download_w(hipStream_t s) const {
   const std::vector<double> f = download_field(0, s);
-  // Paired w updates (k_pcg_b_rows): an odd iteration leaves w^{k+1} = w^k + alpha_k p^k pending
-  // in device memory; apply it here, rounded to the storage type like a device update.
-  // pcg1 (k_pcg1) leaves w_pend_n (1 or 2) steps pending, p^j in p[j & 1], alpha_j in alpha1[j & 3].
-  const PcgState st = read_state(s);
+  // the pending w steps (pending_w), applied here and rounded to the storage type like a device update
+  const PendingW pw = pending_w(read_state(s));
   std::vector<double> pk[2];
-  double a[2] = {0.0, 0.0};
-  int npend = 0;
-  if (pcg1_ && st.w_pend_n > 0 && st.w_pend > 0) {
-    npend = st.w_pend_n;
-    for (int q = 0; q < npend; ++q) {  // q = 0: the oldest pending step
-      const long long j = st.w_pend - (npend - 1) + q;
-      pk[q] = download_field((j & 1) ? 3 : 2, s);
-      a[q] = st.alpha1[j & 3];
-    }
-  } else if (!pcg1_ && st.w_pend > 0) {
-    npend = 1;
-    pk[0] = download_field((st.w_pend & 1) ? 3 : 2, s);
-    a[0] = st.alpha[st.w_pend & 1];
-  }
+  for (int q = 0; q < pw.n; ++q) pk[q] = download_field(pw.field[q], s);
   std::vector<double> out(size_t(sd_.nx) * sd_.ny);
   for (int li = 1; li <= sd_.nx; ++li)
     for (int lj = 1; lj <= sd_.ny; ++lj) {
       const size_t src = size_t(li) * (sd_.ny + 2) + lj;
       double v = f[src];
-      for (int q = 0; q < npend; ++q) v = std::fma(a[q], pk[q][src], v);
-      if (npend && elem_ == 4) v = double(float(v));
+      for (int q = 0; q < pw.n; ++q) v = std::fma(pw.a[q], pk[q][src], v);
+      if (pw.n && plan_.elem == 4) v = double(float(v));
       out[size_t(li - 1) * sd_.ny + (lj - 1)] = v;
     }
   return out;
@@ -1465,21 +1311,15 @@ std::vector<double> GpuSubdomainSolver::download_w(hipStream_t s) const {
 void GpuSubdomainSolver::gather_w_device(double* out, int64_t ld, hipStream_t s) const {
   HIP_CHECK(hipSetDevice(opt_.device));
   PMX_CHECK(out && ld >= spec_.N + 1, "gather_w_device needs an (M+1) x (N+1) array with row stride >= N+1");
-  const PcgState st = read_state(s);
-  const void* pp[2] = {nullptr, nullptr};
-  double a[2] = {0.0, 0.0};
-  const int npend = pending_w(st, pp, a);
+  const PendingW pw = pending_w(read_state(s));
   // the owned nodes, widened by the global boundary row / column where the block touches it
   const int li0 = sd_.gi0() == 0 ? 0 : 1, li1 = sd_.gi0() + sd_.nx + 1 == spec_.M ? sd_.nx + 1 : sd_.nx;
   const int lj0 = sd_.gj0() == 0 ? 0 : 1, lj1 = sd_.gj0() + sd_.ny + 1 == spec_.N ? sd_.ny + 1 : sd_.ny;
-  if (elem_ == 8)
-    launch_gather<double>(static_cast<const double*>(field_base(0)), static_cast<const double*>(pp[0]), a[0],
-                          static_cast<const double*>(pp[1]), a[1], npend, geom_.pitch, out, ld, li0, lj0,
-                          li1 - li0 + 1, lj1 - lj0 + 1, sd_.gi0(), sd_.gj0(), spec_.M, spec_.N, s);
-  else
-    launch_gather<float>(static_cast<const float*>(field_base(0)), static_cast<const float*>(pp[0]), a[0],
-                         static_cast<const float*>(pp[1]), a[1], npend, geom_.pitch, out, ld, li0, lj0,
-                         li1 - li0 + 1, lj1 - lj0 + 1, sd_.gi0(), sd_.gj0(), spec_.M, spec_.N, s);
+  with_storage([&](auto t) {
+    using T = decltype(t);
+    launch_gather<T>(fields<T>().w, pending_p<T>(pw, 0), pw.a[0], pending_p<T>(pw, 1), pw.a[1], pw.n, geom_.pitch, out,
+                     ld, li0, lj0, li1 - li0 + 1, lj1 - lj0 + 1, sd_.gi0(), sd_.gj0(), spec_.M, spec_.N, s);
+  });
   after_launch(s);
 }
 

@@ -3,10 +3,14 @@
 // stage4-mpi+cuda/poisson_mpi_cuda_f.cu:688-983).
 //
 // * GpuSubdomainSolver owns one subdomain's fields on one device: w, r and a ping-pong pair
-//   p0/p1 (4 arrays, 32 B/pt in fp64), the 1D face tables, the block-partials scratch and a
-//   "comm arena" holding the PcgState scalars (the all-reduce buffers) and the packed
-//   send/recv halo buffers.  The arena may be supplied externally (e.g. a torch tensor) so a
-//   Python-side communicator can operate on it.
+//   p0/p1 (4 arrays, 32 B/pt in fp64; pcg1 and the s-step add r2), the 1D face tables, the
+//   block-partials scratch and a "comm arena" holding the PcgState scalars (the all-reduce buffers)
+//   and the packed send/recv halo buffers.  The arena may be supplied externally (e.g. a torch
+//   tensor) so a Python-side communicator can operate on it.  The layout of fields, face fields and
+//   tables is one MemoryPlan (pmx/memory_plan.hpp): the solver allocates from it and takes every
+//   field address from it, and the size estimate evaluates the same type.  Every allocation, stream
+//   and event lives in a move-only owner (DevPtr, HostPtr, Stream, Event below), so a constructor
+//   that throws and the destructor release them in reverse member order.
 // * PcgDriver steps a set of local subdomains through the PCG iteration with a Comm backend,
 //   optionally replaying hipGraph-captured batches of iterations.  The host never waits per
 //   iteration: the stop test runs on the device and later launches become no-ops.
@@ -26,11 +30,20 @@
 #include "pmx/device_types.hpp"
 #include "pmx/geometry.hpp"
 #include "pmx/kernels.hpp"
+#include "pmx/memory_plan.hpp"
 #include "pmx/spec.hpp"
 
 namespace pmx {
 
-enum class DType : int { kFp64 = 0, kFp32 = 1 };
+// Move-only owners of HIP resources.  The deleters ignore the error of a free.
+struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
+struct HostFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+struct StreamFree { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+struct EventFree { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+template <typename T> using DevPtr = std::unique_ptr<T, DevFree>;    // hipMalloc
+template <typename T> using HostPtr = std::unique_ptr<T, HostFree>;  // hipHostMalloc (pinned / mapped)
+using Stream = std::unique_ptr<std::remove_pointer_t<hipStream_t>, StreamFree>;
+using Event = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventFree>;
 
 // Kernel-side view of a subdomain whose fields use row pitch `pitch` (elements).
 DevGeom make_dev_geom(const ProblemSpec& spec, const Subdomain& sd, int64_t pitch);
@@ -40,17 +53,15 @@ DevTables upload_tables(const ProblemSpec& spec, double** owner);
 
 struct GpuOptions {
   int device = 0;
-  int kernel = 1;         // 0: LDS-ring workgroup tiles, 1: wave tiles with DPP lane shifts
-  int block = 256;        // kernel 0: tile width (threads per workgroup)
   // Tile shapes.  pcg_a and pcg_b are separate launches, so each gets its own shape; the *_b
   // fields default to "same as pcg_a" when the pcg_a field is set explicitly.
-  int vec = 0;            // kernel 1, pcg_a: columns per lane (0 = auto: 4 = 32-B fp64 accesses)
-  int waves = 4;          // kernel 1: wave tiles per workgroup
+  int vec = 0;            // pcg_a: columns per lane (0 = auto: 4 = 32-B fp64 accesses)
+  int waves = 4;          // wave tiles per workgroup
   int tile_rows = 0;      // tile height (marching length), 0 = auto-size for occupancy
   int vec_b = 0;          // pcg_b columns per lane (0 = vec if set, else auto: 2 fp64 / 4 fp32)
   int waves_b = 0;        // pcg_b wave tiles per workgroup (0 = waves)
   int tile_rows_b = -1;   // pcg_b tile height (-1 = tile_rows, or 2 for the row kernel)
-  int b_ring = 0;         // kernel 1: 0 = ring-free row kernel for pcg_b (default), 1 = ring kernel
+  int b_ring = 0;         // 0 = ring-free row kernel for pcg_b (default), 1 = ring kernel
   DType dtype = DType::kFp64;
   bool exact = false;     // reference arithmetic order inside the fused kernels
   int graph_batch = 32;   // iterations per captured hipGraph (0 = eager launches)
@@ -66,7 +77,7 @@ struct GpuOptions {
   int pair_w = 1;
   // Iteration algorithm: 2 = pcg2 (k_pcg_a + k_pcg_b, two reductions, radius-1 halo), 1 = pcg1
   // (single-pass k_pcg1, one 5-value reduction, radius-2 halo with corners), -1 = auto (pcg1
-  // where it applies: wave kernels, not exact, any storage type, every subdomain >= 2 x 2 and the 5th
+  // where it applies: not exact, any storage type, every subdomain >= 2 x 2 and the 5th
   // field fits into the device).  The choice depends only on global data (problem, process grid,
   // options, device size), so every rank of a distributed run makes the same one.
   // PMX_ALGO=-1|1|2 overrides.  pcg1 matches the reference iteration counts and pcg2's solution
@@ -241,13 +252,10 @@ class GpuSubdomainSolver {
 
   // ca_gh > 0: the s-step's packed slots (ca_gh ghost lines of z and p per side, ca_gh x ca_gh corners)
   static CommLayout comm_layout(const Subdomain& sd, DType dtype, bool single_pass, int ca_gh = 0);
-  // Upper bound of the device memory a solver for `sd` allocates (fields -- 4, or 5 for the
-  // single-pass iteration -- tables, partials, comm arena).  Checked against hipMemGetInfo before
-  // allocating; used by `pmx --plan` and the pcg1/pcg2 choice.
-  static size_t estimate_device_bytes(const ProblemSpec& spec, const Subdomain& sd, DType dtype,
-                                      bool single_pass);
-  // ... for iteration algorithm `algo` (1 pcg1, 2 pcg2, 3 the s-step PCG: 5 fields with s ghost rows on
-  // strips, plus the two face-coefficient fields)
+  // Upper bound of the device memory a solver for `sd` allocates with iteration algorithm `algo` (1 pcg1,
+  // 2 pcg2, 3 the s-step PCG): its MemoryPlan (the s-step on decomposed grids with the most ghost rows,
+  // 2 kCaMaxS) plus bounds for the partials and the comm arena.  Checked against hipMemGetInfo before
+  // allocating; used by `pmx --plan` and choose_algo.
   static size_t estimate_device_bytes_algo(const ProblemSpec& spec, const Subdomain& sd, DType dtype, int algo);
 
   // r=B, w=0, p=0, state reset, red_b <- (0, zr_0).  Single-pass: the driver then runs the ghost
@@ -306,7 +314,7 @@ class GpuSubdomainSolver {
   // buffers (a row span, padding included, is contiguous).  The driver turns it on when its
   // communicator moves arbitrary device spans (Comm::direct_rows).
   bool can_direct_rows() const {
-    return (pcg1_ || ca_) && (geom_.nb & ~(kNbXlo | kNbXhi)) == 0 && sd_.nx >= (ca_ ? gh_ : 2);
+    return (pcg1_ || ca_) && (geom_.nb & ~(kNbXlo | kNbXhi)) == 0 && sd_.nx >= (ca_ ? plan_.gh : 2);
   }
   void set_direct_rows(bool on);
   bool direct_rows() const { return direct_rows_; }
@@ -407,7 +415,7 @@ class GpuSubdomainSolver {
   };
   CaProbe ca_probe(const std::vector<double>& z, const std::vector<double>& p, const std::vector<double>& w,
                    const std::vector<double>& coef, const std::vector<double>& pa, bool fused, hipStream_t s);
-  int ca_ghost_rows() const { return gh_; }
+  int ca_ghost_rows() const { return plan_.gh; }
   // host mirror of CaState::blk (blocks enqueued): the (z, p) set the next exchange sends
   long long ca_blocks() const { return ca_blk_; }
   void set_ca_blocks(long long b) { ca_blk_ = b; }
@@ -427,24 +435,32 @@ class GpuSubdomainSolver {
   bool w_sweep_next() const { return pcg1_ && host_k_ > 0 && host_k_ % w_cycle() == 0; }
   const TileCfg& tiles_b() const { return tiles_b_; }  // pcg_b
   int device() const { return opt_.device; }
-  size_t field_bytes() const { return field_bytes_; }
+  size_t field_bytes() const { return plan_.field_bytes; }
   const std::vector<float>& placement_ms() const { return placement_ms_; }
   double placement_seconds() const { return placement_s_; }  // wall time of the probe (0: off)
   void* field_base(int which) const;  // pointer to local (0,0)
   size_t device_bytes() const;        // total device memory owned
 
  private:
-  template <typename T> void init_impl(hipStream_t s);
-  template <typename T> void phase_a_impl(hipStream_t s);
-  template <typename T> void phase_b_impl(hipStream_t s, bool pack);
-  template <typename T> void phase_a_kernel_only(hipStream_t s, int part = 0);
-  template <typename T> void phase_b_kernel_only(hipStream_t s, bool pack = true);
+  // f(T{}) with the storage type T of the fields: the one branch on GpuOptions::dtype
+  template <typename F> decltype(auto) with_storage(F&& f) const {
+    return plan_.elem == 8 ? f(double{}) : f(float{});
+  }
+  // the fields at local (0,0), typed (r2: pcg1's second r buffer / the s-step's second z buffer)
+  template <typename T> struct Fields { T *w, *r, *r2, *p0, *p1; };
+  template <typename T> Fields<T> fields() const {
+    auto at = [&](int f) { return reinterpret_cast<T*>(field_ptr(f)); };
+    return {at(0), at(1), plan_.nfields == 5 ? at(4) : nullptr, at(2), at(3)};
+  }
   template <typename T> HaloBufs<T> halo() const;
-  void ca_halo_impl(hipStream_t s, bool unpack);  // k_ca_halo on the (z, p) set the next block reads
-  template <typename T> void halo_impl(hipStream_t s, bool unpack);
+  template <typename T> void init_impl(hipStream_t s);
+  template <typename T> void kernel_a(hipStream_t s, int part = 0);  // k_pcg_a, or the pcg1 sweep
+  template <typename T> void kernel_b(hipStream_t s, bool pack = true);
+  void halo_launch(hipStream_t s, bool unpack);  // k_pcg1_halo, or k_ca_halo on the set the next block reads
+  void ca_pass(hipStream_t s, int kind);         // 0 pass 1, 1 pass 2, 2 fused
+  HaloMsg row_msg(int slot, int order, int f, int nrows, int64_t srow, int64_t rrow) const;  // a direct-row span
   void after_launch(hipStream_t s) const;
   void construct(uintptr_t external_arena);
-  void release() noexcept;  // frees every allocation (destructor, failed constructor)
 
   ProblemSpec spec_;
   Subdomain sd_;
@@ -457,23 +473,26 @@ class GpuSubdomainSolver {
   TileCfg tiles1_{};   // pcg1
   TileCfg tiles1w_{};  // pcg1, the w-moving sweeps (GpuOptions::rows1w / pf1w)
   const TileCfg& tiles1_for(bool wsweep) const { return wsweep ? tiles1w_ : tiles1_; }
+  // pcg1's five reduction weights: h1 h2 for the four sums, the norm's weight for the difference
+  struct Weights5 { double v[5]; };
+  Weights5 weights1() const {
+    const double h = g_.h1h2;
+    return {{h, h, h, h, spec_.norm == Norm::kWeighted ? h : 1.0}};
+  }
   bool pcg1_ = false;
   bool ca_ = false;             // s-step PCG
   CaTiles ca_tiles_{};
-  unsigned* ca_tbl_ = nullptr;  // its row-class table
-  unsigned* ca_tbl_f_ = nullptr;  // ... of the fused pass's tiling
-  char* ca_faces_ = nullptr;    // its face-coefficient fields (a, b)
-  hipStream_t ca_side_ = nullptr;  // the frame tiles' stream (split kernels)
-  hipEvent_t ca_ev_fork_ = nullptr, ca_ev_join_ = nullptr;
-  hipEvent_t ca_frame_wait_ = nullptr;  // one-shot: the next pass 1's frame tiles wait for it
-  template <typename T> void ca_pass_impl(hipStream_t s, int kind);  // 0 pass 1, 1 pass 2, 2 fused
-  size_t ca_face_bytes_ = 0;    // one face-coefficient field (fp64)
-  CaState* ca_state_ = nullptr;
+  DevPtr<unsigned> ca_tbl_;     // its row-class table
+  DevPtr<unsigned> ca_tbl_f_;   // ... of the fused pass's tiling
+  DevPtr<char> ca_faces_;       // its face-coefficient fields (a, b)
+  Stream ca_side_;              // the frame tiles' stream (split kernels)
+  Event ca_ev_fork_, ca_ev_join_;
+  hipEvent_t ca_frame_wait_ = nullptr;  // one-shot: the next pass 1's frame tiles wait for it (not owned)
+  DevPtr<CaState> ca_state_;
   CaState ca_init_{};           // host template of the state init() uploads
-  double* ca_chunk_ = nullptr;  // its reduction's chunk sums
+  DevPtr<double> ca_chunk_;     // its reduction's chunk sums
   long long ca_blk_ = 0;        // blocks enqueued since init (CaState::blk's host mirror)
   bool ca_primed_ = false;      // partials_ hold the next block's Gram sums from a batch-ending fused pass
-  int gh_ = 2;                  // ghost rows of the fields on each side
   bool ca_fuse_ = false;        // the s-step's fused pass (GpuOptions::ca_fuse, decided at construction)
   // the s-step kernels' geometry and face tables: geom_ / tables_, or under ca_dirichlet a standalone
   // grid of the subdomain's rows (gi0 = 0, M = nx + 1, tables shifted by gi0), whose rows 0 and nx + 1
@@ -492,39 +511,46 @@ class GpuSubdomainSolver {
   const double* dev_f_ = nullptr;
   const double* dev_w_ = nullptr;
   int64_t dev_ld_f_ = 0, dev_ld_w_ = 0;
-  // pending w steps as download_w applies them: fields and factors, returns their number
-  int pending_w(const PcgState& st, const void* pp[2], double a[2]) const;
+  // pending w steps as download_w applies them, oldest first: the p fields (2 or 3) and their factors
+  struct PendingW {
+    int n = 0, field[2] = {2, 2};
+    double a[2] = {0.0, 0.0};
+  };
+  PendingW pending_w(const PcgState& st) const;
+  // step q's p field for a kernel, null when no such step is pending
+  template <typename T> const T* pending_p(const PendingW& pw, int q) const {
+    return q < pw.n ? reinterpret_cast<const T*>(field_ptr(pw.field[q])) : nullptr;
+  }
   CommLayout layout_{};
-  size_t elem_ = 8, field_bytes_ = 0, field_off_ = 0;
-  // Fields w, r, p0, p1 (and pcg1's r2) in ONE allocation, field f at fields_ + f * field_stride_;
-  // rows -1 .. nx+2 each.
-  char* fields_ = nullptr;
-  char* r2_ = nullptr;      // pcg1 only: the second r buffer (r is double-buffered there)
-  size_t field_stride_ = 0;
+  // Layout of the fields (w, r, p0, p1 and pcg1's / the s-step's r2, in ONE allocation), the face fields
+  // and the tables; every address below comes from it
+  MemoryPlan plan_;
+  DevPtr<char> fields_;
+  char* field_ptr(int f, int64_t li = 0, int64_t lj = 0) const { return fields_.get() + plan_.at(f, li, lj); }
+  char* field_raw(int f) const { return fields_.get() + size_t(f) * plan_.field_bytes; }  // field f's first byte
   bool block1_ = false;       // pcg1 sweeps as block tiles (pcg1_block.hip)
   bool block_fused_ = false;  // ... which also finish the reduction (no k_reduce_n launch)
-  char* field_raw(int f) const { return fields_ + size_t(f) * field_stride_; }
   void place_fields();                // placement probe (see gpu_solver.hip)
   void probe_iterations(hipStream_t s, hipEvent_t e0, hipEvent_t e1);
   std::vector<float> placement_ms_;   // probe: ms per candidate block (the kept one is the min)
   double placement_s_ = 0.0;
-  double* tables_buf_ = nullptr;
-  double* partials_ = nullptr;
+  DevPtr<double> tables_buf_;
+  DevPtr<double> partials_;
   size_t npart_ = 0;
   double* reduce_ws_ = nullptr;  // k_reduce chunk sums + ticket (inside the partials allocation)
+  DevPtr<char> arena_own_;       // the comm arena, unless it was supplied externally
   char* arena_ = nullptr;
-  bool own_arena_ = true;
-  PcgState* state_ = nullptr;
-  Pcg1Slot* tile_order_ = nullptr;    // pcg1 dispatch order + row classes (pcg1_build_order)
-  Pcg1Slot* tile_order_w_ = nullptr;  // ... of tiles1w_ when its shape differs
+  PcgState* state_ = nullptr;    // inside the arena
+  DevPtr<Pcg1Slot> tile_order_;    // pcg1 dispatch order + row classes (pcg1_build_order)
+  DevPtr<Pcg1Slot> tile_order_w_;  // ... of tiles1w_ when its shape differs
   int slow_tiles_ = 0;
 #ifdef PMX_WAVE_TRACE
   void* wtrace_ = nullptr;
   int wtrace_n_ = 0;
 #endif
-  PcgState* host_state_ = nullptr;  // pinned
-  long long* progress_host_ = nullptr;  // host-mapped, coherent (GpuOptions::progress)
-  long long* progress_dev_ = nullptr;   // its device address, or nullptr (off)
+  HostPtr<PcgState> host_state_;     // pinned
+  HostPtr<long long> progress_host_;  // host-mapped, coherent (GpuOptions::progress)
+  long long* progress_dev_ = nullptr;  // its device address, or nullptr (off)
 };
 
 // ---------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include "pmx/cpu_pcg.hpp"
 #include "pmx/decomp.hpp"
 #include "pmx/geometry.hpp"
+#include "pmx/memory_plan.hpp"
 #include "pmx/report.hpp"
 #include "pmx/spec.hpp"
 
@@ -143,6 +144,47 @@ void test_spec_validation() {
   CHECK(t.effective_max_iter() == 7);
 }
 
+// MemoryPlan: the conditions the solver's kernels rely on, for every algorithm, storage type and ghost-row
+// count, on one grid, 2 x 2 blocks and row strips
+void test_memory_plan() {
+  const int grids[][2] = {{40, 40}, {97, 130}, {16384, 16384}};
+  const struct { int world; Split split; } decomps[] = {{1, Split::kAuto}, {4, Split::kReference}, {8, Split::kRows}};
+  for (const auto& mn : grids)
+    for (const auto& dc : decomps)
+      for (int rank : {0, dc.world - 1})
+        for (DType dtype : {DType::kFp64, DType::kFp32})
+          for (int algo : {1, 2, 3})
+            for (int gh : {2, 3, 6}) {
+              ProblemSpec spec;
+              spec.M = mn[0];
+              spec.N = mn[1];
+              const Subdomain sd = decompose_2d(spec.M, spec.N, make_process_grid(dc.world, spec.M, spec.N, dc.split), rank);
+              const MemoryPlan p(spec, sd, dtype, algo, gh);
+              const bool blocks = algo == 3 && sd.grid.Py > 1;  // s-step 2-D blocks: gh ghost columns per side
+              const int64_t cols = blocks ? gh : 1;             // ghost columns on each side
+              CHECK(p.elem == (dtype == DType::kFp64 ? 8u : 4u) && p.align * p.elem == 256 && p.gh == gh);
+              CHECK(p.nfields == (algo == 2 ? 4 : 5) && (p.face_bytes != 0) == (algo == 3));
+              // column 1 of every row of every field (and face field) starts a 256-B line of the allocation
+              bool aligned = true;
+              for (int f = 0; f < p.nfields; ++f)
+                for (int64_t li = 1 - gh; li <= sd.nx + gh; ++li) aligned = aligned && p.at(f, li, 1) % 256 == 0;
+              for (int f = 0; f < 2 && algo == 3; ++f)
+                for (int64_t li = 1 - gh; li <= sd.nx + gh; ++li) aligned = aligned && p.face_at(f, li, 1) % 256 == 0;
+              CHECK(aligned);
+              // a field holds its first ghost row from its leftmost column to its last row's rightmost one
+              CHECK(int64_t(p.field_off) + (1 - gh) * p.pitch - (cols - 1) >= 0);
+              CHECK(p.at(0, sd.nx + gh, sd.ny + cols) + p.elem <= p.field_bytes);
+              CHECK(p.at(1, 1 - gh, 1 - cols) >= p.field_bytes);  // ... and the next field starts behind it
+              if (algo == 3) CHECK(p.face_at(0, sd.nx + gh, sd.ny + cols) + 8 <= p.face_bytes);
+              // 2-D blocks: a row's right ghost columns end before the next row's left ones begin
+              if (blocks) CHECK(p.at(0, 0, sd.ny + gh) < p.at(0, 1, -gh));
+              CHECK(p.row_bytes() == size_t(p.pitch) * p.elem && p.pitch >= sd.ny + 2 + 8);
+              const size_t tables = (4 * size_t(spec.M + 2) + 4 * size_t(spec.N + 2)) * 8 + 8 * size_t(spec.M + 2) * 4;
+              CHECK(p.table_bytes == tables);
+              CHECK(p.total() == size_t(p.nfields) * p.field_bytes + 2 * p.face_bytes + tables);
+            }
+}
+
 }  // namespace
 
 int main() {
@@ -152,6 +194,7 @@ int main() {
   test_cpu_goldens();
   test_report_formats();
   test_spec_validation();
+  test_memory_plan();
   std::printf("pmx_unit_tests: %d checks, %d failed\n", g_checks, g_failed);
   return g_failed ? 1 : 0;
 }

@@ -53,3 +53,47 @@ def test_max_square_grid_by_algorithm(native):
     assert auto == g1 > g3 > 60000          # auto falls back to pcg1: its 5 fields bound the grid
     assert native.max_square_grid(288e9, 8, "fp64", 0.1, 3) > 2.8 * g3
     assert native.max_square_grid(288e9, 1, "fp32", 0.1, 1) > 1.4 * g1
+
+
+# estimate_device_bytes for algo 1, 2, 3 by (grid, world, split, rank, dtype), recorded before the layout
+# moved into MemoryPlan (pmx/memory_plan.hpp): the plan must not move a byte, or choose_algo decides otherwise
+ESTIMATES = {
+    ((40, 40), 1, "auto", 0, "fp64"): (1177608, 1147144, 1222992),
+    ((40, 40), 1, "auto", 0, "fp32"): (1118472, 1101064, 1163856),
+    ((40, 40), 4, "reference", 0, "fp64"): (1093752, 1081208, 1193136),
+    ((40, 40), 4, "reference", 0, "fp32"): (1091704, 1081208, 1141936),
+    ((40, 40), 4, "reference", 3, "fp64"): (1092472, 1080184, 1189552),
+    ((40, 40), 4, "reference", 3, "fp32"): (1090424, 1080184, 1139632),
+    ((40, 40), 8, "rows", 0, "fp64"): (1085792, 1075808, 1139728),
+    ((40, 40), 8, "rows", 0, "fp32"): (1072224, 1065568, 1107728),
+    ((40, 40), 8, "rows", 7, "fp64"): (1083192, 1073720, 1136144),
+    ((40, 40), 8, "rows", 7, "fp32"): (1070904, 1064504, 1105424),
+    ((97, 130), 1, "auto", 0, "fp64"): (1738552, 1586744, 1997920),
+    ((97, 130), 1, "auto", 0, "fp32"): (1468216, 1378872, 1778784),
+    ((97, 130), 4, "reference", 0, "fp64"): (1280016, 1227536, 1436528),
+    ((97, 130), 4, "reference", 0, "fp32"): (1206288, 1172240, 1366896),
+    ((97, 130), 4, "reference", 3, "fp64"): (1278992, 1226512, 1435504),
+    ((97, 130), 4, "reference", 3, "fp32"): (1205264, 1171216, 1365872),
+    ((97, 130), 8, "rows", 0, "fp64"): (1185672, 1149576, 1339264),
+    ((97, 130), 8, "rows", 0, "fp32"): (1135496, 1114760, 1261440),
+    ((97, 130), 8, "rows", 7, "fp64"): (1185672, 1149576, 1339264),
+    ((97, 130), 8, "rows", 7, "fp32"): (1135496, 1114760, 1261440),
+    ((16384, 16384), 1, "auto", 0, "fp64"): (10851075776, 8695855808, 15169038016),
+    ((16384, 16384), 1, "auto", 0, "fp32"): (5479286464, 4399577792, 9805638848),
+    ((16384, 16384), 4, "reference", 0, "fp64"): (2722019304, 2181212904, 3811676912),
+    ((16384, 16384), 4, "reference", 0, "fp32"): (1378138088, 1106684648, 2468586224),
+    ((16384, 16384), 4, "reference", 3, "fp64"): (2721526464, 2180785856, 3811192512),
+    ((16384, 16384), 4, "reference", 3, "fp32"): (1377809088, 1106388672, 2468265152),
+    ((16384, 16384), 8, "rows", 0, "fp64"): (1362906048, 1091649216, 1915719712),
+    ((16384, 16384), 8, "rows", 0, "fp32"): (689327040, 553434816, 1238212640),
+    ((16384, 16384), 8, "rows", 7, "fp64"): (1362249408, 1091123904, 1914752704),
+    ((16384, 16384), 8, "rows", 7, "fp32"): (688998080, 553171648, 1237572800),
+}
+
+
+@pytest.mark.parametrize("case", list(ESTIMATES), ids=lambda c: "-".join(str(x) for x in c[0] + c[1:]))
+def test_memory_plan_estimates_are_pinned(native, spec, case):
+    (M, N), world, split, rank, dtype = case
+    got = tuple(native.estimate_device_bytes(spec(M, N), world, getattr(native.Split, split), rank, dtype, algo)
+                for algo in (1, 2, 3))
+    assert got == ESTIMATES[case]

@@ -167,7 +167,7 @@ def test_d4_nothing_is_retained(pkg, data, cfg):
     s.solve(rhs=d["f_dev"], w0=d["w0_dev"])
     s.residual_norm(d["f_dev"])
     s.w_tensor()
-    assert s.device_bytes == before == DEVICE_BYTES[cfg]
+    assert s.device_bytes == before == DEVICE_BYTES[cfg, "fp64", 1]
 
 
 @pytest.mark.parametrize("ranks", [1, 4])

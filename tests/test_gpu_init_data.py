@@ -222,8 +222,23 @@ def test_g6_checkpoint_carries_the_data(pkg, oracle, tmp_path):
     assert np.array_equal(b.gather_local_w(), whole.gather_local_w())
 
 
-# device_bytes of a 97 x 130 session without the placement probe, as before this feature
-DEVICE_BYTES = {"ca-s3": 949800, "pcg1-march": 693088, "pcg2": 541280}
+# device_bytes of a 97 x 130 session without the placement probe by (cfg, dtype, ranks), as before this
+# feature; the fp32 and 4-rank entries were recorded before the layout moved into MemoryPlan
+DEVICE_BYTES = {
+    ("ca-s3", "fp64", 1): 949800, ("pcg1-march", "fp64", 1): 693088, ("pcg2", "fp64", 1): 541280,
+    ("ca-s3", "fp64", 4): 1565120, ("pcg1-march", "fp64", 4): 940160, ("pcg2", "fp64", 4): 730240,
+    ("ca-s3", "fp32", 1): 730664, ("pcg1-march", "fp32", 1): 421472, ("pcg2", "fp32", 1): 331488,
+    ("ca-s3", "fp32", 4): 1286592, ("pcg1-march", "fp32", 4): 645248, ("pcg2", "fp32", 4): 509056,
+}
+
+
+def _estimate(pkg, grid, cfg, dtype, ranks):
+    """Sum over the ranks of native.estimate_device_bytes: an upper bound of device_bytes."""
+    native = pkg.load_native()
+    spec = pkg.PoissonEllipse(M=grid[0], N=grid[1]).to_native()
+    algo = {"ca": 3, "pcg1": 1, "pcg2": 2}[CONFIGS[cfg]["algo"]]
+    return sum(native.estimate_device_bytes(spec, ranks, getattr(native.Split, RANKS[ranks]), r, dtype, algo)
+               for r in range(ranks))
 
 
 @pytest.mark.parametrize("cfg", ALGOS)
@@ -233,7 +248,20 @@ def test_g7_nothing_is_retained(pkg, oracle, cfg):
     before = s.device_bytes
     s.solve(rhs=oracle[grid]["f"], w0=10.0 * oracle[grid]["const"].w)
     s.residual_norm(oracle[grid]["f"])
-    assert s.device_bytes == before == DEVICE_BYTES[cfg]
+    assert s.device_bytes == before == DEVICE_BYTES[cfg, "fp64", 1]
+    assert s.device_bytes <= _estimate(pkg, grid, cfg, "fp64", 1)
+
+
+@pytest.mark.parametrize("ranks", [1, 4])
+@pytest.mark.parametrize("dtype", ["fp64", "fp32"])
+@pytest.mark.parametrize("cfg", ALGOS)
+def test_allocated_bytes_are_pinned_and_below_the_estimate(pkg, cfg, dtype, ranks):
+    """What a session allocates is what it allocated before the memory plan, and the estimate that sizes the
+    algorithm choice bounds it (here by its 1 MiB term alone)."""
+    grid = (97, 130)
+    s = _session(pkg, grid, cfg, ranks, dtype=dtype, placement=0)
+    assert s.device_bytes == DEVICE_BYTES[cfg, dtype, ranks]
+    assert s.device_bytes <= _estimate(pkg, grid, cfg, dtype, ranks)
 
 
 @pytest.mark.parametrize("arg", ["rhs", "w0"])

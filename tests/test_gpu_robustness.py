@@ -1,9 +1,11 @@
 """Checkpoint/resume and the halo-poison debug mode (§5.2) on the GPU path."""
+import hashlib
 import os
 import subprocess
 
 import numpy as np
 import pytest
+import torch
 
 from conftest import ROOT, sub
 
@@ -101,3 +103,40 @@ def test_resume_with_pending_w_step_is_bitwise(pkg, tmp_path, steps):
     rb = b.solve_checkpointed(path, every=0, resume=True)
     assert rb["iters"] == rr["iters"] == 546
     assert np.array_equal(b.gather_local_w(), ref.gather_local_w())
+
+
+# SHA-256 of the checkpoint a 40 x 40 fp64 session with eager launches writes after init and `steps`
+# iterations, recorded before the layout moved into MemoryPlan (two runs gave the same files).  pcg1 and
+# pcg2 stop with w steps pending; the s-step at a block boundary, where it accepts the save.
+CHECKPOINT_SHA256 = {
+    "ca": (6, "909ff7bf95364f0cbb4129843c7b2fa930e306970d2a27474057088faf8e35f4"),
+    "pcg1": (7, "0b884aafdfed9a114cd58064c58b4814dc41953d3953606655e6808069cc7f87"),
+    "pcg2": (7, "6ec4c9d83d89c23362b2c51b32489d0f25a1ec964b29c28be6153ae2cdc181e1"),
+}
+
+
+@pytest.mark.parametrize("algo", list(CHECKPOINT_SHA256))
+def test_checkpoint_file_is_bytewise_unchanged(pkg, tmp_path, algo):
+    steps, sha = CHECKPOINT_SHA256[algo]
+    kw = dict(block_tiles=0) if algo == "pcg1" else {}
+    s = sub("models").make_session(pkg.PoissonEllipse(M=40, N=40), algo=algo, graph_batch=0, **kw)
+    s.init()
+    s.step(steps)
+    s.synchronize()
+    if algo != "ca":
+        assert s.state()["w_pend"] == steps
+    path = str(tmp_path / "ck.bin")
+    s.save_checkpoint(path)
+    with open(path, "rb") as f:
+        assert hashlib.sha256(f.read()).hexdigest() == sha
+
+
+def test_constructor_that_fails_late_leaves_a_usable_process(pkg, native):
+    """The arena's alignment is checked after the fields, tables and partials are allocated: the failed
+    constructor releases them, and the next solver works."""
+    p = pkg.PoissonEllipse(M=40, N=40)
+    arena = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
+    with pytest.raises(RuntimeError, match="256-B aligned"):
+        native.SubdomainSolver(p.to_native(), arena=arena.data_ptr() + 8)
+    r = pkg.solve(p, "hip")
+    assert r.iters == 50 and r.status == "converged"
