@@ -429,6 +429,21 @@ PYBIND11_MODULE(_pmx, m) {
         }, py::arg("spec"), py::arg("nranks"), py::arg("split") = Split::kReference,
         py::arg("threads") = 1, py::arg("keep_solution") = true, py::arg("rhs") = py::none(),
         py::arg("w0") = py::none());
+  // x, y: C-contiguous (M+1) x (N+1) float64 arrays, validated by the caller (PoissonEllipse.apply); no
+  // finiteness scan -- a NaN of x propagates to the nodes whose stencil reads it
+  m.def("cpu_apply", [](const ProblemSpec& s, py::array_t<double, py::array::c_style> x, py::object y, double alpha,
+                        double beta, double gamma, double c0) {
+          s.validate();
+          auto fits = [&](const py::array& a) { return a.ndim() == 2 && a.shape(0) == s.M + 1 && a.shape(1) == s.N + 1; };
+          py::array_t<double, py::array::c_style> ya;
+          if (!y.is_none()) ya = y.cast<py::array_t<double, py::array::c_style>>();
+          if (!fits(x) || (!y.is_none() && !fits(ya))) throw py::value_error("x and y must have shape (M+1, N+1)");
+          const double *xp = x.data(), *yp = y.is_none() ? nullptr : ya.data();
+          std::vector<double> r;
+          { py::gil_scoped_release nogil; r = cpu_apply(s, xp, yp, alpha, beta, gamma, c0); }
+          return to_numpy(r, {s.M + 1, s.N + 1});
+        }, py::arg("spec"), py::arg("x"), py::arg("y") = py::none(), py::arg("alpha") = 1.0, py::arg("beta") = 0.0,
+        py::arg("gamma") = 1.0, py::arg("const") = 0.0);
   m.def("cpu_assemble", [](const ProblemSpec& s) {
     std::vector<double> a, b, B;
     cpu_assemble(s, a, b, B);
@@ -757,6 +772,40 @@ PYBIND11_MODULE(_pmx, m) {
            "the solution gather_local_w() returns, bitwise, as a torch.float64 tensor on the session's device, "
            "written by a kernel without passing through the host; out: a tensor to fill (see gather_w_device) "
            "instead of a new one.  Usable at once on the current torch stream")
+      .def("apply", [](py::object self, py::object x, py::object out, double alpha, double beta, py::object y,
+                       double gamma, double c0) {
+             Session& s = self.cast<Session&>();
+             const ProblemSpec& sp = s.solver(0).spec();
+             const int dev = s.solver(0).device();
+             auto field = [&](const py::object& o, const char* name, bool writable) {
+               if (!py::hasattr(o, "__cuda_array_interface__"))
+                 throw py::value_error(std::string(name) + " must be a float64 device tensor of shape (M+1, N+1)");
+               return device_field(o, sp, dev, name, writable);
+             };
+             for (double v : {alpha, beta, gamma, c0})
+               if (!std::isfinite(v)) throw py::value_error("alpha, beta, gamma and const must be finite");
+             const UserField fx = field(x, "x", false);
+             const UserField fy = y.is_none() ? UserField() : field(y, "y", false);
+             if (out.is_none()) {
+               const py::module_ torch = py::module_::import("torch");
+               out = torch.attr("empty")(py::make_tuple(sp.M + 1, sp.N + 1), py::arg("dtype") = torch.attr("float64"),
+                                         py::arg("device") = torch.attr("device")("cuda", dev));
+             }
+             const UserField fo = field(out, "out", true);
+             { py::gil_scoped_release g; s.apply_device(fx, fo, fy, alpha, beta, gamma, c0); }
+             return out;
+           }, py::arg("x"), py::arg("out") = py::none(), py::kw_only(), py::arg("alpha") = 1.0, py::arg("beta") = 0.0,
+           py::arg("y") = py::none(), py::arg("gamma") = 1.0, py::arg("const") = 0.0,
+           "out <- alpha L x + beta x + gamma y + const on the interior nodes and 0 on the box boundary, L = A + sigma I "
+           "with the session's sigma: the plain matrix on the whole box, fictitious region included, no ellipse mask.  "
+           "x, y (optional) and out are float64 device arrays of shape (M+1, N+1) on the session's device (unit column "
+           "stride, row stride >= N+1; elements past column N of a row of out are not touched); out is allocated when "
+           "omitted, may be y, must not overlap x, and is returned.  Boundary values of x count as 0 and are never "
+           "read.  x is not scanned for non-finite values: a NaN propagates to the nodes whose stencil reads it.  "
+           "Evaluated in fp64 for every storage type of the session, one kernel per subdomain, with no exchange; the "
+           "session's fields, state and device_bytes are untouched.  Stream order as gather_w_device: inputs after "
+           "their producers' streams, out usable at once on its stream; the call does not wait.  ValueError, before "
+           "any launch, for a wrong dtype, shape, stride or device, an overlapping out or a non-finite scalar")
       .def("step", [](Session& s, int64_t n) { py::gil_scoped_release g; s.step(n); })
       .def("synchronize", [](Session& s) { py::gil_scoped_release g; s.synchronize(); })
       .def("solve", [](Session& s, int poll, py::object rhs, py::object w0) {

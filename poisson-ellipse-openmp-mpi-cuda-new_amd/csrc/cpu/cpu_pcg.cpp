@@ -181,6 +181,42 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
   return res;
 }
 
+std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const double* y, double alpha, double beta,
+                              double gamma, double c0) {
+  spec.validate();
+  const GridInfo g(spec);
+  const geo::FaceTables t(spec, g);
+  const int M = spec.M, N = spec.N;
+  const int P = N + 2, Q = N + 1;  // pitch of the ghosted arrays / of the global ones
+  const size_t n = size_t(M + 2) * P;
+  const double h1 = g.h1, h2 = g.h2, sigma = spec.sigma;
+  std::vector<double> a(n), b(n), p(n, 0.0), out(size_t(M + 1) * Q, 0.0);
+  for (int i = 0; i <= M + 1; ++i)
+    for (int j = 0; j <= N + 1; ++j) {
+      a[size_t(i) * P + j] = geo::coef_a(t, g, i, j);
+      b[size_t(i) * P + j] = geo::coef_b(t, g, i, j);
+    }
+  for (int i = 1; i <= M - 1; ++i)
+    for (int j = 1; j <= N - 1; ++j) p[size_t(i) * P + j] = x[size_t(i) * Q + j];
+  const bool plain = alpha == 1.0 && beta == 0.0 && !y && c0 == 0.0;
+  for (int i = 1; i <= M - 1; ++i)
+    for (int j = 1; j <= N - 1; ++j) {
+      const size_t c = size_t(i) * P + j;
+      const double Ax = -1.0 / h1 * (a[c + P] * (p[c + P] - p[c]) / h1 - a[c] * (p[c] - p[c - P]) / h1);
+      const double Ay = -1.0 / h2 * (b[c + 1] * (p[c + 1] - p[c]) / h2 - b[c] * (p[c] - p[c - 1]) / h2);
+      const double Lx = sigma != 0.0 ? (Ax + Ay) + sigma * p[c] : Ax + Ay;
+      double v = Lx;
+      if (!plain) {
+        v = alpha * Lx;
+        v = std::fma(beta, p[c], v);
+        if (y) v = std::fma(gamma, y[size_t(i) * Q + j], v);
+        v += c0;
+      }
+      out[size_t(i) * Q + j] = v;
+    }
+  return out;
+}
+
 // ---------------------------------------------------------------------------
 // CpuSubdomain (stage2-mpi/poisson_mpi_decomp.cpp:124-232 semantics)
 // ---------------------------------------------------------------------------

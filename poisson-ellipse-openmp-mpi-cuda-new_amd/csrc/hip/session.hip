@@ -324,6 +324,10 @@ void Session::gather_w_device(double* out, int64_t ld, hipStream_t consumer) {
   synchronize();
   wait_for(consumer);  // earlier work on the consumer's stream may still use `out`
   for (size_t i = 0; i < solvers_.size(); ++i) solvers_[i]->gather_w_device(out, ld, stream_of(int(i)));
+  hand_over(consumer);
+}
+
+void Session::hand_over(hipStream_t consumer) {
   hipEvent_t e = nullptr;
   HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   hipError_t err = hipSuccess;
@@ -333,6 +337,50 @@ void Session::gather_w_device(double* out, int64_t ld, hipStream_t consumer) {
   }
   (void)hipEventDestroy(e);
   HIP_CHECK(err);
+}
+
+void Session::apply_device(const UserField& x, const UserField& out, const UserField& y, double alpha, double beta,
+                           double gamma, double c0) {
+  require_connected();
+  const int M = cfg_.spec.M, N = cfg_.spec.N;
+  if (cfg_.comm != CommKind::kSelf && cfg_.comm != CommKind::kLocal)
+    throw std::invalid_argument("apply needs a session that owns every subdomain (world 1 or the local "
+                                "communicator); multi-process sessions are not supported");
+  for (auto& sp : solvers_)
+    if (sp->device() != solvers_[0]->device())
+      throw std::invalid_argument("apply needs every subdomain of the session on the tensors' device");
+  for (const UserField* f : {&x, &out, &y}) {
+    if (f == &y && !y) continue;
+    if (!*f || !f->on_device) throw std::invalid_argument("apply: x, out and y are device fields");
+    if (f->ld != 0 && f->ld < N + 1) throw std::invalid_argument("apply: row stride of a device field below N + 1");
+  }
+  if (!(std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma) && std::isfinite(c0)))
+    throw std::invalid_argument("apply: alpha, beta, gamma and const must be finite");
+  auto ld = [&](const UserField& f) { return f.ld ? f.ld : int64_t(N) + 1; };
+  auto span = [&](const UserField& f) { return (int64_t(M) * ld(f) + N + 1) * int64_t(sizeof(double)); };
+  const char *xb = reinterpret_cast<const char*>(x.ptr), *ob = reinterpret_cast<const char*>(out.ptr);
+  if (xb < ob + span(out) && ob < xb + span(x)) throw std::invalid_argument("apply: out overlaps x");
+  if (y && !(y.ptr == out.ptr && ld(y) == ld(out))) {  // out may BE y: every lane reads its element before writing it
+    const char* yb = reinterpret_cast<const char*>(y.ptr);
+    if (yb < ob + span(out) && ob < yb + span(y)) throw std::invalid_argument("apply: out overlaps y without being y");
+  }
+
+  // inputs after their producers' work, and after whatever the consumer's stream still does with out
+  wait_for(x.stream);
+  if (y && y.stream != x.stream) wait_for(y.stream);
+  if (out.stream != x.stream && !(y && out.stream == y.stream)) wait_for(out.stream);
+  ApplyCoef K;
+  K.alpha = alpha; K.beta = beta; K.gamma = y ? gamma : 0.0; K.c0 = c0; K.sigma = cfg_.spec.sigma;
+  K.plain = alpha == 1.0 && beta == 0.0 && !y && c0 == 0.0;
+  for (size_t i = 0; i < solvers_.size(); ++i) {
+    // the owned nodes, widened by the global boundary row / column where the block touches it (as k_gather)
+    const Subdomain& sd = solvers_[i]->sd();
+    const int i0 = sd.gi0() == 0 ? 0 : sd.gi0() + 1, i1 = sd.gi0() + sd.nx + 1 == M ? M : sd.gi0() + sd.nx;
+    const int j0 = sd.gj0() == 0 ? 0 : sd.gj0() + 1, j1 = sd.gj0() + sd.ny + 1 == N ? N : sd.gj0() + sd.ny;
+    launch_apply(solvers_[i]->geom(), solvers_[i]->tables(), x.ptr, ld(x), y.ptr, y ? ld(y) : 0,
+                 const_cast<double*>(out.ptr), ld(out), i0, j0, i1 - i0 + 1, j1 - j0 + 1, K, stream_of(int(i)));
+  }
+  hand_over(out.stream);
 }
 
 void Session::step(int64_t n) {

@@ -42,6 +42,14 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads = 1, bool keep_soluti
 void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<double>& b,
                   std::vector<double>& B);
 
+// The operator itself, the host twin of Session::apply_device: alpha L x + beta x + gamma y + c0 on the interior
+// nodes and 0 on the box boundary of a global (M+1) x (N+1) row-major array, L = A + spec.sigma I -- the plain
+// matrix on the whole box, no ellipse mask -- in cpu_solve's mat_A arithmetic.  Boundary values of x count as 0
+// and are not read; y may be null (no y term).  Combination order: v = alpha Lx; v = fma(beta, x, v);
+// v = fma(gamma, y, v) with y; v += c0 -- and Lx itself for alpha = 1, beta = 0, no y, c0 = 0.
+std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const double* y = nullptr, double alpha = 1.0,
+                              double beta = 0.0, double gamma = 1.0, double c0 = 0.0);
+
 // One rank's block (local arrays (nx+2) x (ny+2), row-major, pitch ny+2).
 class CpuSubdomain {
  public:

@@ -318,4 +318,18 @@ void launch_gather(const T* w, const T* pa, double ca, const T* pb, double cb, i
                    double* out, int64_t ld, int li0, int lj0, int rows, int cols, int gi0, int gj0, int M, int N,
                    hipStream_t s);
 
+// The operator on device tensors (apply_kernels.hip).  Global rows gi_lo .. gi_lo + rows - 1 and columns
+// gj_lo .. gj_lo + cols - 1 of out (row stride ldo) <- alpha (A + sigma I) x + beta x + gamma y + c0 on
+// interior nodes, 0 on the box boundary; x, y (null: no y term; may be out), out are global (M+1) x (N+1)
+// fp64 arrays with unit column stride, x read as 0 on the box boundary and never loaded there.  G supplies
+// M, N and the mesh constants, Tb the global face tables; sigma != 0 launches the kernel built for it.
+// plain: alpha = 1, beta = 0, no y, c0 = 0 -- (A + sigma I) x itself is stored.
+struct ApplyCoef {
+  double alpha = 1.0, beta = 0.0, gamma = 0.0, c0 = 0.0, sigma = 0.0;
+  int plain = 1;
+};
+void launch_apply(const DevGeom& G, const DevTables& Tb, const double* x, int64_t ldx, const double* y, int64_t ldy,
+                  double* out, int64_t ldo, int gi_lo, int gj_lo, int rows, int cols, const ApplyCoef& K,
+                  hipStream_t s);
+
 }  // namespace pmx

@@ -90,6 +90,17 @@ class Session {
   // elements past column N of a row are not touched.  Stream order as UserField describes for an
   // output on `consumer`; returns without waiting for the kernels.  Sessions that own every subdomain.
   void gather_w_device(double* out, int64_t ld, hipStream_t consumer);
+  // The operator on device tensors: out <- alpha L x + beta x + gamma y + c0 on the interior nodes, 0 on the
+  // box boundary, L = A + sigma I with the session's sigma -- the plain matrix on the whole box, no ellipse
+  // mask.  x, y (may be empty: no y term; may be out's memory) and out are global (M+1) x (N+1) fp64
+  // device fields (UserField; out must not overlap x).  Boundary values of x count as 0 and are never
+  // loaded.  One k_apply launch per subdomain (apply_kernels.hip), each block reading x across subdomain
+  // borders straight from the global array: no exchange.  Evaluated in fp64 whatever the session's storage
+  // type.  Stream order as UserField describes: x and y are inputs, out an output on out.stream; returns
+  // without waiting.  Touches no field, state or partials of the session; nothing is allocated.
+  // std::invalid_argument unless the session owns every subdomain (self / local communicator) on one device.
+  void apply_device(const UserField& x, const UserField& out, const UserField& y, double alpha, double beta,
+                    double gamma, double c0);
   void step(int64_t n);
   void synchronize();
   RunStats solve(int poll_batches = 1);
@@ -150,6 +161,7 @@ class Session {
   void require_owns_all(const char* what) const;  // self / local communicator
   int require_one_device() const;        // the device every solver lives on (device fields need one)
   void wait_for(hipStream_t producer);   // every session stream waits for `producer`'s work so far
+  void hand_over(hipStream_t consumer);  // `consumer` waits for every session stream's work so far
   // throws std::invalid_argument naming the first device field with a non-finite value
   void check_finite(const UserField& rhs, const UserField& w0);
 

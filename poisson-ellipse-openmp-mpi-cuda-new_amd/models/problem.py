@@ -162,6 +162,47 @@ class PoissonEllipse:
             raise ValueError(f"{name} holds non-finite values")
         return np.ascontiguousarray(a)
 
+    def _host_array(self, a, name: str, writable: bool = False) -> np.ndarray:
+        """field()'s type, dtype and shape rules without its finiteness scan (apply's arguments)."""
+        if hasattr(a, "numpy") and hasattr(a, "device"):  # a torch tensor
+            if a.device.type != "cpu":
+                raise ValueError(f"{name}: device tensors are not supported, pass a NumPy array or a CPU tensor "
+                                 "(Session.apply takes device tensors)")
+            a = a.detach().numpy()
+        if not isinstance(a, np.ndarray):
+            raise ValueError(f"{name} must be a NumPy array or a CPU torch tensor")
+        if a.dtype != np.float64:
+            raise ValueError(f"{name} must have dtype float64, got {a.dtype}")
+        if a.shape != (self.M + 1, self.N + 1):
+            raise ValueError(f"{name} must have shape (M+1, N+1) = {(self.M + 1, self.N + 1)}, got {a.shape}")
+        if writable and not a.flags.writeable:
+            raise ValueError(f"{name} is read-only")
+        return a
+
+    def apply(self, x, out=None, *, alpha: float = 1.0, beta: float = 0.0, y=None, gamma: float = 1.0,
+              const: float = 0.0) -> np.ndarray:
+        """alpha L x + beta x + gamma y + const on the interior nodes and 0 on the box boundary, on the host
+        (the CPU oracle's stencil); L = A + sigma I with this problem's sigma, the plain matrix on the whole
+        box -- fictitious region included, no ellipse mask.  The host twin of Session.apply: NumPy arrays
+        (or CPU tensors) of shape (M+1, N+1) float64 in, a NumPy array out (`out` when given; it may be y
+        and must not overlap x).  Boundary values of x count as 0 and are not read.  x is not scanned for
+        non-finite values: a NaN propagates to the nodes whose stencil reads it."""
+        xa = self._host_array(x, "x")
+        ya = None if y is None else self._host_array(y, "y")
+        oa = None if out is None else self._host_array(out, "out", writable=True)
+        for name, v in (("alpha", alpha), ("beta", beta), ("gamma", gamma), ("const", const)):
+            if not (isinstance(v, (int, float)) and math.isfinite(v)):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        if oa is not None and np.may_share_memory(oa, xa):
+            raise ValueError("out overlaps x")
+        r = _native().cpu_apply(self.to_native(), np.ascontiguousarray(xa),
+                                None if ya is None else np.ascontiguousarray(ya), float(alpha), float(beta),
+                                float(gamma), float(const))
+        if oa is None:
+            return r
+        oa[...] = r
+        return oa
+
     def error_norms(self, w: np.ndarray, exact: Optional[np.ndarray] = None) -> dict:
         """L2 (h-weighted) and max error of a (M+1)x(N+1) solution in D, vs the analytic solution of the
         constant-F problem or, for another right-hand side, vs `exact` ((M+1)x(N+1) values of its solution)."""
