@@ -39,7 +39,9 @@ struct FieldArg {
   py::array_t<double, py::array::c_style> arr;  // owns (or shares) the data `ptr` points to
   const double* ptr = nullptr;
 };
-FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::string& name) {
+// reaction: a reaction field instead -- the same type, dtype and shape rules; finite and >= 0 on the interior
+// nodes, its box-boundary values ignored and not read.
+FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::string& name, bool reaction = false) {
   FieldArg f;
   if (obj.is_none()) return f;
   py::object a = obj;
@@ -58,8 +60,17 @@ FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::strin
   f.arr = py::array_t<double, py::array::c_style>::ensure(arr);
   if (!f.arr) throw py::value_error(name + ": cannot be read as a C-contiguous float64 array");
   const double* d = f.arr.data();
-  for (py::ssize_t k = 0; k < f.arr.size(); ++k)
-    if (!std::isfinite(d[k])) throw py::value_error(name + " holds non-finite values");
+  if (reaction) {
+    for (int i = 1; i <= s.M - 1; ++i)
+      for (int j = 1; j <= s.N - 1; ++j) {
+        const double v = d[py::ssize_t(i) * (s.N + 1) + j];
+        if (!(std::isfinite(v) && v >= 0.0))
+          throw py::value_error(name + " must be finite and >= 0 on every interior node");
+      }
+  } else {
+    for (py::ssize_t k = 0; k < f.arr.size(); ++k)
+      if (!std::isfinite(d[k])) throw py::value_error(name + " holds non-finite values");
+  }
   f.ptr = d;
   return f;
 }
@@ -123,16 +134,19 @@ struct SessionField {
   FieldArg host;
   UserField f;
 };
-SessionField session_field(const py::object& obj, Session& s, const std::string& name) {
+SessionField session_field(const py::object& obj, const ProblemSpec& sp, int device, const std::string& name,
+                           bool reaction = false) {
   SessionField r;
-  const ProblemSpec& sp = s.solver(0).spec();
   if (!obj.is_none() && py::hasattr(obj, "__cuda_array_interface__")) {
-    r.f = device_field(obj, sp, s.solver(0).device(), name);
+    r.f = device_field(obj, sp, device, name);
   } else {
-    r.host = field_arg(obj, sp, name);
+    r.host = field_arg(obj, sp, name, reaction);
     r.f = UserField(r.host.ptr);
   }
   return r;
+}
+SessionField session_field(const py::object& obj, Session& s, const std::string& name) {
+  return session_field(obj, s.solver(0).spec(), s.solver(0).device(), name);
 }
 
 // The Python-orchestrated paths (OpContext ops, SubdomainSolver + comm_layout under DistGpuPCG
@@ -411,39 +425,47 @@ PYBIND11_MODULE(_pmx, m) {
 
   // ---- CPU oracle ----
   // rhs / w0: optional (M+1) x (N+1) float64 arrays, see pmx/cpu_pcg.hpp
-  m.def("cpu_solve", [](const ProblemSpec& s, int threads, bool keep, py::object rhs, py::object w0) {
+  // reaction: optional (M+1) x (N+1) float64 field c >= 0 (interior nodes; the boundary is not read)
+  m.def("cpu_solve", [](const ProblemSpec& s, int threads, bool keep, py::object rhs, py::object w0,
+                        py::object reaction) {
           s.validate();
           const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
+          const FieldArg c = field_arg(reaction, s, "reaction", true);
           SolveResult r;
-          { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep, f.ptr, w.ptr); }
+          { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep, f.ptr, w.ptr, c.ptr); }
           return result_dict(r, s, keep);
         }, py::arg("spec"), py::arg("threads") = 1, py::arg("keep_solution") = true,
-        py::arg("rhs") = py::none(), py::arg("w0") = py::none());
+        py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("reaction") = py::none());
   m.def("cpu_solve_decomposed", [](const ProblemSpec& s, int nranks, Split split, int threads, bool keep,
-                                   py::object rhs, py::object w0) {
+                                   py::object rhs, py::object w0, py::object reaction) {
           s.validate();
           const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
+          const FieldArg c = field_arg(reaction, s, "reaction", true);
           SolveResult r;
-          { py::gil_scoped_release nogil; r = cpu_solve_decomposed(s, nranks, split, threads, keep, f.ptr, w.ptr); }
+          {
+            py::gil_scoped_release nogil;
+            r = cpu_solve_decomposed(s, nranks, split, threads, keep, f.ptr, w.ptr, c.ptr);
+          }
           return result_dict(r, s, keep);
         }, py::arg("spec"), py::arg("nranks"), py::arg("split") = Split::kReference,
         py::arg("threads") = 1, py::arg("keep_solution") = true, py::arg("rhs") = py::none(),
-        py::arg("w0") = py::none());
+        py::arg("w0") = py::none(), py::arg("reaction") = py::none());
   // x, y: C-contiguous (M+1) x (N+1) float64 arrays, validated by the caller (PoissonEllipse.apply); no
   // finiteness scan -- a NaN of x propagates to the nodes whose stencil reads it
   m.def("cpu_apply", [](const ProblemSpec& s, py::array_t<double, py::array::c_style> x, py::object y, double alpha,
-                        double beta, double gamma, double c0) {
+                        double beta, double gamma, double c0, py::object reaction) {
           s.validate();
+          const FieldArg c = field_arg(reaction, s, "reaction", true);
           auto fits = [&](const py::array& a) { return a.ndim() == 2 && a.shape(0) == s.M + 1 && a.shape(1) == s.N + 1; };
           py::array_t<double, py::array::c_style> ya;
           if (!y.is_none()) ya = y.cast<py::array_t<double, py::array::c_style>>();
           if (!fits(x) || (!y.is_none() && !fits(ya))) throw py::value_error("x and y must have shape (M+1, N+1)");
           const double *xp = x.data(), *yp = y.is_none() ? nullptr : ya.data();
           std::vector<double> r;
-          { py::gil_scoped_release nogil; r = cpu_apply(s, xp, yp, alpha, beta, gamma, c0); }
+          { py::gil_scoped_release nogil; r = cpu_apply(s, xp, yp, alpha, beta, gamma, c0, c.ptr); }
           return to_numpy(r, {s.M + 1, s.N + 1});
         }, py::arg("spec"), py::arg("x"), py::arg("y") = py::none(), py::arg("alpha") = 1.0, py::arg("beta") = 0.0,
-        py::arg("gamma") = 1.0, py::arg("const") = 0.0);
+        py::arg("gamma") = 1.0, py::arg("const") = 0.0, py::arg("reaction") = py::none());
   m.def("cpu_assemble", [](const ProblemSpec& s) {
     std::vector<double> a, b, B;
     cpu_assemble(s, a, b, B);
@@ -557,6 +579,23 @@ PYBIND11_MODULE(_pmx, m) {
   }, py::arg("spec"), py::arg("world") = 1, py::arg("split") = Split::kAuto, py::arg("rank") = 0,
      py::arg("dtype") = "fp64", py::arg("algo") = 1);
 
+  // The MemoryPlan of one subdomain of a pcg1 session (tests of the layout): sizes, and the byte offsets of
+  // local (0, 0) of every field from the start of the fields; reaction: with the shift field
+  m.def("memory_plan", [](const ProblemSpec& s, int world, Split split, int rank, const std::string& dtype,
+                          bool reaction) {
+    const Subdomain sd = decompose_2d(s.M, s.N, make_process_grid(world, s.M, s.N, split), rank);
+    const MemoryPlan p(s, sd, dtype == "fp64" ? DType::kFp64 : DType::kFp32, 1, 2, reaction);
+    py::dict d;
+    d["elem"] = p.elem; d["pitch"] = p.pitch; d["gh"] = p.gh; d["nx"] = sd.nx; d["ny"] = sd.ny;
+    d["field_bytes"] = p.field_bytes; d["nfields"] = p.nfields; d["shift_field"] = p.shift_field();
+    d["fields_total"] = p.fields_total(); d["total"] = p.total();
+    py::list at;
+    for (int f = 0; f < p.nfields + p.nshift; ++f) at.append(p.at(f));
+    d["at"] = at;
+    return d;
+  }, py::arg("spec"), py::arg("world") = 1, py::arg("split") = Split::kReference, py::arg("rank") = 0,
+     py::arg("dtype") = "fp64", py::arg("reaction") = false);
+
   py::class_<OpContext>(m, "OpContext", py::module_local())
       .def(py::init<const ProblemSpec&, int, int, int, int64_t, int>(), py::arg("spec"),
            py::arg("Px"), py::arg("Py"), py::arg("rank"), py::arg("pitch"), py::arg("device") = 0)
@@ -638,8 +677,16 @@ PYBIND11_MODULE(_pmx, m) {
                        bool rccl_graph, bool overlap, int vec_b, int waves_b, int tile_rows_b,
                        bool poison_halos, bool b_ring, int algo, bool defer_connect, int threaded,
                        int placement, double placement_budget_s, double placement_keep_free, int sharing,
-                       int block_tiles, int ca_s, int split_sweep) {
+                       int block_tiles, int ca_s, int split_sweep, py::object reaction) {
              SessionConfig c;
+             s.validate();
+             // type, dtype, shape, stride and device of the field (and a host field's values) before anything
+             // else; the Session checks a device field's values, still before it allocates
+             const SessionField rf = session_field(reaction, s, devices.empty() ? device : devices[0], "reaction", true);
+             c.reaction = rf.f.ptr;
+             c.reaction_ld = rf.f.ld;
+             c.reaction_on_device = rf.f.on_device;
+             c.reaction_stream = rf.f.stream;
              c.sharing = sharing;
              c.spec = s;
              c.opt = make_options(device, kernel, block, vec, waves, tile_rows, dtype, exact,
@@ -675,7 +722,18 @@ PYBIND11_MODULE(_pmx, m) {
            py::arg("b_ring") = false, py::arg("algo") = -1, py::arg("defer_connect") = false,
            py::arg("threaded") = -1, py::arg("placement") = 0, py::arg("placement_budget_s") = 0.5,
            py::arg("placement_keep_free") = 0.5, py::arg("sharing") = 0, py::arg("block_tiles") = -1,
-           py::arg("ca_s") = 3, py::arg("split_sweep") = -1)
+           py::arg("ca_s") = 3, py::arg("split_sweep") = -1, py::arg("reaction") = py::none())
+      .def("set_reaction", [](Session& s, py::object reaction) {
+             if (reaction.is_none()) throw py::value_error("reaction must be an (M+1) x (N+1) float64 field");
+             const SessionField rf = session_field(reaction, s.solver(0).spec(), s.solver(0).device(), "reaction", true);
+             py::gil_scoped_release g;
+             s.set_reaction(rf.f);
+           }, py::arg("reaction"),
+           "replace the reaction field c of a session built with one (make_session(p, reaction=c)): the same "
+           "types and checks as there (a NumPy array, a CPU tensor or a float64 device array; finite and >= 0 on "
+           "the interior nodes, ValueError before the session is touched).  The shift field is rewritten in place, "
+           "so captured graphs stay valid; step() raises until the next init() / solve()")
+      .def_property_readonly("has_reaction", &Session::has_reaction)
       .def("ca_probe",
            [](Session& s, int i, py::array_t<double, py::array::c_style | py::array::forcecast> z,
               py::array_t<double, py::array::c_style | py::array::forcecast> p,

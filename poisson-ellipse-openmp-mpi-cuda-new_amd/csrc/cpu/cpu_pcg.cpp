@@ -57,7 +57,7 @@ void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<d
 }
 
 SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, const double* rhs,
-                      const double* w0) {
+                      const double* w0, const double* reaction) {
   spec.validate();
   const GridInfo g(spec);
   const geo::FaceTables t(spec, g);
@@ -68,6 +68,16 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
   const double sigma = spec.sigma;  // screened problem: A + sigma I, D + sigma (0: the reference's operator)
   const int nt = threads < 1 ? 1 : threads;
   (void)nt;
+  // reaction field: the shift of node c is sh[c] = sigma + c(x, y) in sigma's place, through the same
+  // expressions (a constant field: the sigma solve, bitwise)
+  std::vector<double> shv;
+  if (reaction) {
+    shv.assign(n, 0.0);
+    for (int i = 1; i <= M - 1; ++i)
+      for (int j = 1; j <= N - 1; ++j) shv[size_t(i) * P + j] = sigma + reaction[size_t(i) * (N + 1) + j];
+  }
+  const double* sh = reaction ? shv.data() : nullptr;
+  const bool shifted = sigma != 0.0 || sh;
 
   std::vector<double> a(n), b(n), w(n, 0.0), r(n, 0.0), z(n, 0.0), p(n, 0.0), Ap(n, 0.0),
       wprev(n, 0.0);
@@ -96,7 +106,8 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
     for (int i = 1; i <= M - 1; ++i)
       for (int j = 1; j <= N - 1; ++j) {
         const size_t c = size_t(i) * P + j;
-        const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + sigma;
+        const double s = sh ? sh[c] : sigma;
+        const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + s;
         z[c] = (D != 0.0) ? r[c] / D : 0.0;
       }
   };
@@ -107,7 +118,8 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
         const size_t c = size_t(i) * P + j;
         const double Ax = -1.0 / h1 * (a[c + P] * (p[c + P] - p[c]) / h1 - a[c] * (p[c] - p[c - P]) / h1);
         const double Ay = -1.0 / h2 * (b[c + 1] * (p[c + 1] - p[c]) / h2 - b[c] * (p[c] - p[c - 1]) / h2);
-        Ap[c] = sigma != 0.0 ? (Ax + Ay) + sigma * p[c] : Ax + Ay;
+        const double s = sh ? sh[c] : sigma;
+        Ap[c] = shifted ? (Ax + Ay) + s * p[c] : Ax + Ay;
       }
   };
 
@@ -182,7 +194,7 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
 }
 
 std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const double* y, double alpha, double beta,
-                              double gamma, double c0) {
+                              double gamma, double c0, const double* reaction) {
   spec.validate();
   const GridInfo g(spec);
   const geo::FaceTables t(spec, g);
@@ -204,7 +216,8 @@ std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const do
       const size_t c = size_t(i) * P + j;
       const double Ax = -1.0 / h1 * (a[c + P] * (p[c + P] - p[c]) / h1 - a[c] * (p[c] - p[c - P]) / h1);
       const double Ay = -1.0 / h2 * (b[c + 1] * (p[c + 1] - p[c]) / h2 - b[c] * (p[c] - p[c - 1]) / h2);
-      const double Lx = sigma != 0.0 ? (Ax + Ay) + sigma * p[c] : Ax + Ay;
+      const double s = reaction ? sigma + reaction[size_t(i) * Q + j] : sigma;
+      const double Lx = (sigma != 0.0 || reaction) ? (Ax + Ay) + s * p[c] : Ax + Ay;
       double v = Lx;
       if (!plain) {
         v = alpha * Lx;
@@ -222,7 +235,7 @@ std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const do
 // ---------------------------------------------------------------------------
 
 CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads, const double* rhs,
-                           const double* w0)
+                           const double* w0, const double* reaction)
     : spec_(spec), g_(spec), sd_(sd), threads_(threads < 1 ? 1 : threads) {
   const geo::FaceTables t(spec, g_);
   const int nx = sd.nx, ny = sd.ny, P = ny + 2;
@@ -243,6 +256,12 @@ CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int thr
       B_[size_t(li) * P + lj] = !rhs ? geo::rhs(t, spec, gi, gj)
                                 : geo::rhs_mask(t, spec, gi, gj) ? rhs[size_t(gi) * (spec.N + 1) + gj] : 0.0;
     }
+  if (reaction) {
+    sh_.assign(n, 0.0);
+    for (int li = 1; li <= nx; ++li)
+      for (int lj = 1; lj <= ny; ++lj)
+        sh_[size_t(li) * P + lj] = spec.sigma + reaction[size_t(sd.gi0() + li) * (spec.N + 1) + sd.gj0() + lj];
+  }
   if (w0) {  // with the ring, straight from the global array (boundary nodes count as 0)
     w0_.assign(n, 0.0);
     for (int li = 0; li <= nx + 1; ++li)
@@ -278,6 +297,8 @@ double CpuSubdomain::matvec_dot() {
   const int nx = sd_.nx, ny = sd_.ny, P = ny + 2, nt = threads_;
   const double h1 = g_.h1, h2 = g_.h2, sigma = spec_.sigma;
   const double* a = a_.data(); const double* b = b_.data(); const double* p = p_.data();
+  const double* sh = sh_.empty() ? nullptr : sh_.data();
+  const bool shifted = sigma != 0.0 || sh;
   double* Ap = Ap_.data();
   double sum = 0.0;
 #pragma omp parallel for collapse(2) reduction(+ : sum) num_threads(nt) if (nt > 1)
@@ -286,7 +307,8 @@ double CpuSubdomain::matvec_dot() {
       const size_t c = size_t(li) * P + lj;
       const double Ax = -1.0 / h1 * (a[c + P] * (p[c + P] - p[c]) / h1 - a[c] * (p[c] - p[c - P]) / h1);
       const double Ay = -1.0 / h2 * (b[c + 1] * (p[c + 1] - p[c]) / h2 - b[c] * (p[c] - p[c - 1]) / h2);
-      Ap[c] = sigma != 0.0 ? (Ax + Ay) + sigma * p[c] : Ax + Ay;
+      const double s = sh ? sh[c] : sigma;
+      Ap[c] = shifted ? (Ax + Ay) + s * p[c] : Ax + Ay;
       sum += Ap[c] * p[c];
     }
   return sum * h1 * h2;
@@ -314,13 +336,14 @@ double CpuSubdomain::precond_dot() {
   const int nx = sd_.nx, ny = sd_.ny, P = ny + 2, nt = threads_;
   const double h1 = g_.h1, h2 = g_.h2, sigma = spec_.sigma;
   const double* a = a_.data(); const double* b = b_.data(); const double* r = r_.data();
+  const double* sh = sh_.empty() ? nullptr : sh_.data();
   double* z = z_.data();
   double sum = 0.0;
 #pragma omp parallel for collapse(2) reduction(+ : sum) num_threads(nt) if (nt > 1)
   for (int li = 1; li <= nx; ++li)
     for (int lj = 1; lj <= ny; ++lj) {
       const size_t c = size_t(li) * P + lj;
-      const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + sigma;
+      const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + (sh ? sh[c] : sigma);
       z[c] = (D != 0.0) ? r[c] / D : 0.0;
       sum += z[c] * r[c];
     }
@@ -331,12 +354,13 @@ double CpuSubdomain::rhs_dot() const {
   const int nx = sd_.nx, ny = sd_.ny, P = ny + 2, nt = threads_;
   const double h1 = g_.h1, h2 = g_.h2, sigma = spec_.sigma;
   const double* a = a_.data(); const double* b = b_.data(); const double* B = B_.data();
+  const double* sh = sh_.empty() ? nullptr : sh_.data();
   double sum = 0.0;
 #pragma omp parallel for collapse(2) reduction(+ : sum) num_threads(nt) if (nt > 1)
   for (int li = 1; li <= nx; ++li)
     for (int lj = 1; lj <= ny; ++lj) {
       const size_t c = size_t(li) * P + lj;
-      const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + sigma;
+      const double D = (a[c + P] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2) + (sh ? sh[c] : sigma);
       const double z = (D != 0.0) ? B[c] / D : 0.0;
       sum += z * B[c];
     }
@@ -441,13 +465,13 @@ SolveResult cpu_pcg_loop(const ProblemSpec& spec, std::vector<CpuSubdomain*>& lo
 
 SolveResult cpu_solve_decomposed(const ProblemSpec& spec, int nranks, Split split,
                                  int threads_per_rank, bool keep_solution, const double* rhs,
-                                 const double* w0) {
+                                 const double* w0, const double* reaction) {
   spec.validate();
   const ProcGrid pg = make_process_grid(nranks, spec.M, spec.N, split);
   std::vector<CpuSubdomain> subs;
   subs.reserve(nranks);
   for (int r = 0; r < nranks; ++r)
-    subs.emplace_back(spec, decompose_2d(spec.M, spec.N, pg, r), threads_per_rank, rhs, w0);
+    subs.emplace_back(spec, decompose_2d(spec.M, spec.N, pg, r), threads_per_rank, rhs, w0, reaction);
   std::vector<CpuSubdomain*> local;
   for (auto& s : subs) local.push_back(&s);
 

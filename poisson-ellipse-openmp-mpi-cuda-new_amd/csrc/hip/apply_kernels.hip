@@ -21,6 +21,11 @@
 // Faces from the 1-D tables as k_init forms them (load_col, load_row, face_a, face_b); a(i+1, j) of one
 // row is a(i, j) of the next, bitwise, and is carried over.  (A x) is apply_a<true>, the reference's
 // operation order without contraction; sigma enters as ONE fma on top, as apply_a_sh.
+//
+// SH = 2 (a session with a reaction field): the shift of a node is read from the shift field T(sigma + c) of
+// the subdomain that owns the launch's block (ApplyCoef::shift, its pitch and local origin) with the step's
+// other loads, and enters in sigma's place -- so apply, the solver and residual_norm share one operator,
+// for fp32 storage too.  SH = 0 / 1 are the kernels they were.
 #include <cmath>
 #include <cstdint>
 
@@ -55,7 +60,7 @@ __device__ __forceinline__ double combine(const ApplyCoef& K, double Lx, double 
 }  // namespace
 
 // block: global rows gi_lo .. gi_lo + rows - 1, columns gj_lo .. gj_lo + cols - 1, inside [0, M] x [0, N]
-template <bool SH, bool HAS_Y>
+template <int SH, bool HAS_Y, typename T = double>
 __global__ void __launch_bounds__(kApplyCols)
 k_apply(DevGeom G, DevTables Tb, const double* __restrict__ x, int64_t ldx, const double* y, int64_t ldy,
         double* out, int64_t ldo, int gi_lo, int gj_lo, int rows, int cols, ApplyCoef K) {
@@ -95,12 +100,19 @@ k_apply(DevGeom G, DevTables Tb, const double* __restrict__ x, int64_t ldx, cons
 
   for (int rb = r0; rb < rend; rb += kApplyUnroll) {
     double xp[kApplyUnroll], ep[kApplyUnroll], yv[kApplyUnroll];
+    [[maybe_unused]] T sv[kApplyUnroll];
     // the step's loads: rows rb + 1 .. rb + U of x (centre and edge column), rows rb .. rb + U - 1 of y
 #pragma unroll
     for (int u = 0; u < kApplyUnroll; ++u) xp[u] = *xptr(gi_lo + rb + u + 1, gjc);
     if constexpr (HAS_Y) {
 #pragma unroll
       for (int u = 0; u < kApplyUnroll; ++u) yv[u] = y[int64_t(min(gi_lo + rb + u, gi_last)) * ldy + gjs];
+    }
+    if constexpr (SH == 2) {  // local (gi - sgi0, gj - sgj0) of the owning subdomain: its nodes and boundary lines
+      const T* sh = static_cast<const T*>(K.shift);
+#pragma unroll
+      for (int u = 0; u < kApplyUnroll; ++u)
+        sv[u] = sh[int64_t(min(gi_lo + rb + u, gi_last) - K.sgi0) * K.spitch + (gjs - K.sgj0)];
     }
 #pragma unroll
     for (int u = 0; u < kApplyUnroll; ++u) ep[u] = 0.0;
@@ -119,7 +131,8 @@ k_apply(DevGeom G, DevTables Tb, const double* __restrict__ x, int64_t ldx, cons
       const double a1 = face_a(cc, rc.rv1, G);
       const double b0 = face_b(rc, cc.rh0, G), b1 = face_b(rc, cc.rh1, G);
       double Lx = apply_a<true>(xc, xm, xn, xjm, xjp, a0, a1, b0, b1, G);
-      if constexpr (SH) Lx = __builtin_fma(K.sigma, xc, Lx);  // as apply_a_sh
+      if constexpr (SH == 2) Lx = __builtin_fma(double(sv[u]), xc, Lx);
+      else if constexpr (SH == 1) Lx = __builtin_fma(K.sigma, xc, Lx);  // as apply_a_sh
       const double v = jin && rowin(gi) ? combine<HAS_Y>(K, Lx, xc, HAS_Y ? yv[u] : 0.0) : 0.0;
       if (owned) out[int64_t(gi) * ldo + gjs] = v;
       xm = xc;
@@ -141,12 +154,19 @@ void launch_apply(const DevGeom& G, const DevTables& Tb, const double* x, int64_
   PMX_CHECK(gy <= 65535, "too many rows for one launch: " << rows);
   const dim3 grid(unsigned((cols + kApplyCols - 1) / kApplyCols), unsigned(gy)), block(kApplyCols);
   const bool sh = K.sigma != 0.0;
-#define PMX_APPLY(SH, HY) \
-  hipLaunchKernelGGL((k_apply<SH, HY>), grid, block, 0, s, G, Tb, x, ldx, y, ldy, out, ldo, gi_lo, gj_lo, rows, cols, K)
-  if (sh && y) PMX_APPLY(true, true);
-  else if (sh) PMX_APPLY(true, false);
-  else if (y) PMX_APPLY(false, true);
-  else PMX_APPLY(false, false);
+#define PMX_APPLY(...) \
+  hipLaunchKernelGGL((k_apply<__VA_ARGS__>), grid, block, 0, s, G, Tb, x, ldx, y, ldy, out, ldo, gi_lo, gj_lo, rows, cols, K)
+  if (K.shift) {
+    PMX_CHECK(K.selem == 8 || K.selem == 4, "k_apply: the shift field is fp64 or fp32");
+    if (K.selem == 8 && y) PMX_APPLY(2, true, double);
+    else if (K.selem == 8) PMX_APPLY(2, false, double);
+    else if (y) PMX_APPLY(2, true, float);
+    else PMX_APPLY(2, false, float);
+  }
+  else if (sh && y) PMX_APPLY(1, true);
+  else if (sh) PMX_APPLY(1, false);
+  else if (y) PMX_APPLY(0, true);
+  else PMX_APPLY(0, false);
 #undef PMX_APPLY
   HIP_CHECK(hipGetLastError());
 }

@@ -214,10 +214,10 @@ GpuOptions resolve_options(const GpuOptions& in) {
 
 void apply_sigma_rules(const ProblemSpec& spec, const ProcGrid& grid, GpuOptions& o) {
   PMX_CHECK(o.resolved, "apply_sigma_rules needs resolve_options()");
-  if (spec.sigma == 0.0) return;
+  if (spec.sigma == 0.0 && !o.reaction) return;
   auto refuse = [&](const char* option) {
-    throw std::invalid_argument(std::string("sigma != 0 (the screened problem) runs pcg1 on the row march only: ") +
-                                option + " is not built for it");
+    throw std::invalid_argument(std::string(o.reaction ? "a reaction field" : "sigma != 0 (the screened problem)") +
+                                " runs pcg1 on the row march only: " + option + " is not built for it");
   };
   if (o.algo == 3) refuse("algo=\"ca\" (the s-step PCG)");
   if (o.algo == 2) refuse("algo=\"pcg2\"");
@@ -337,12 +337,12 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
   const int gh = ca_ && sd.grid.size() > 1 ? (ca_fuse_ ? 2 * opt_.ca_s : opt_.ca_s) : 2;
   PMX_CHECK(!pcg1_ || (!opt.exact && (sd.grid.size() == 1 || (sd.nx >= 2 && sd.ny >= 2))),
             "pcg1 needs the fast arithmetic and a subdomain of at least 2 x 2 nodes");
-  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh);
+  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh, opt_.reaction != 0);
   const int elem = int(plan_.elem);
   geom_ = make_dev_geom(spec, sd, plan_.pitch);
   const DevGeom& G = geom_;
   {  // fail with a sizing message instead of a bare hipErrorOutOfMemory
-    const size_t need = estimate_device_bytes_algo(spec, sd, opt.dtype, opt_.algo);
+    const size_t need = estimate_device_bytes_algo(spec, sd, opt.dtype, opt_.algo) + plan_.nshift * plan_.field_bytes;
     PMX_CHECK(need <= free_b,
               "subdomain " << sd.nx << "x" << sd.ny << " (" << (ca_ ? "s-step, 7" : pcg1_ ? "pcg1, 5" : "pcg2, 4")
                            << " fields) needs " << need / 1e9 << " GB on device " << opt.device
@@ -682,6 +682,39 @@ void GpuSubdomainSolver::set_init_data(const double* f, const double* w0, int64_
   dev_f_ = dev_w_ = nullptr;  // each call replaces the data of the next init
 }
 
+void GpuSubdomainSolver::set_reaction(const double* c, int64_t ld, bool on_device, hipStream_t s) {
+  PMX_CHECK(has_reaction(), "set_reaction needs a solver built with a reaction field (GpuOptions::reaction)");
+  PMX_CHECK(c && ld >= spec_.N + 1, "set_reaction needs an (M+1) x (N+1) array with row stride >= N+1");
+  HIP_CHECK(hipSetDevice(opt_.device));
+  // the block with its radius-2 frame (local rows -1 .. nx+2, columns -1 .. ny+2), clipped to the interior
+  // nodes of the box; everything else of the field is 0
+  const int gi_lo = std::max(1, sd_.gi0() - 1), gi_hi = std::min(spec_.M - 1, sd_.gi0() + sd_.nx + 2);
+  const int gj_lo = std::max(1, sd_.gj0() - 1), gj_hi = std::min(spec_.N - 1, sd_.gj0() + sd_.ny + 2);
+  const int rows = gi_hi - gi_lo + 1, cols = gj_hi - gj_lo + 1;
+  const int f = plan_.shift_field();
+  const double* src = c + int64_t(gi_lo) * ld + gj_lo;
+  char* dst = field_ptr(f, gi_lo - sd_.gi0(), gj_lo - sd_.gj0());
+  HIP_CHECK(hipMemsetAsync(field_raw(f), 0, plan_.field_bytes, s));
+  std::vector<char> stage;  // the host path: T(sigma + c), dense, until s has copied it
+  if (on_device) {
+    with_storage([&](auto t) {
+      using T = decltype(t);
+      launch_scatter_shift<T>(src, ld, reinterpret_cast<T*>(dst), plan_.pitch, rows, cols, spec_.sigma, s);
+    });
+  } else {
+    stage.resize(size_t(rows) * size_t(cols) * plan_.elem);
+    with_storage([&](auto t) {
+      using T = decltype(t);
+      T* o = reinterpret_cast<T*>(stage.data());
+      for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < cols; ++j) o[size_t(i) * cols + j] = static_cast<T>(spec_.sigma + src[int64_t(i) * ld + j]);
+    });
+    HIP_CHECK(hipMemcpy2DAsync(dst, plan_.row_bytes(), stage.data(), size_t(cols) * plan_.elem, size_t(cols) * plan_.elem,
+                               size_t(rows), hipMemcpyHostToDevice, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
 void GpuSubdomainSolver::set_init_data_device(const double* f, const double* w0, int64_t ld_f, int64_t ld_w0) {
   PMX_CHECK(!f || ld_f >= sd_.ny, "row stride of the device right-hand side below the block's width");
   PMX_CHECK(!w0 || ld_w0 >= sd_.ny + 2, "row stride of the device initial guess below the block's width");
@@ -730,6 +763,7 @@ double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_
     X.cb = pw.a[1];
     X.npend = pw.n;
     X.sigma = spec_.sigma;
+    X.shift = shift<T>();
     launch_init_data<T>(geom_, tables_, fields<T>().w, nullptr, HaloBufs<T>{}, part, init_tiles_, X, true, s);
   });
   HIP_CHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -842,7 +876,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
   // recovered p^{k-2} carries the STORAGE rounding of p^{k-1} and r^{k-1} times 1 / beta_{k-1}: with fp32
   // fields w then misses the oracle by 2.7e-6 max|w| where re-reading p^{k-2} gives 7e-8 (measured, 40x40
   // and 97x130, constant rhs).  There the sweep re-reads below beta = 0.5 (growth <= 3 roundings).
-  if (spec_.sigma != 0.0 && sizeof(T) == 4 && opt_.pair_w != 2) st.pair_min_beta = 0.5;
+  if ((spec_.sigma != 0.0 || has_reaction()) && sizeof(T) == 4 && opt_.pair_w != 2) st.pair_min_beta = 0.5;
   st.w_cycle = w_cycle();
   // stop rule: the step rule leaves PcgState's tail zero, as every build before it did
   stop_ref_data_ = false;
@@ -873,6 +907,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     X.has_f = !stage_f_.empty() || dev_f_;
     X.has_w = !stage_w_.empty() || dev_w_;
     X.sigma = spec_.sigma;
+    X.shift = shift<T>();
     X.rho_b = stop_ref_data_ ? 1 : 0;
     // the same cells from either source: a staged host copy, or the caller's device block through the
     // scatter kernel (set_init_data_device)
@@ -899,7 +934,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     std::vector<char>().swap(stage_w_);
     dev_f_ = dev_w_ = nullptr;
   } else {
-    launch_init<T>(G, tables_, w, r, halo<T>(), partials_.get(), init_tiles_, s, spec_.sigma);
+    launch_init<T>(G, tables_, w, r, halo<T>(), partials_.get(), init_tiles_, s, spec_.sigma, shift<T>());
     after_launch(s);
   }
   // red_b[1] = (z^0, r^0); red_b[0] = rho_B = (D^-1 B, B) when the residual rule starts from a w0, else 0
@@ -990,7 +1025,7 @@ void GpuSubdomainSolver::kernel_a(hipStream_t s, int part) {
   }
   if (pcg1_)
     launch_pcg1<T>(geom_, tables_, F.w, F.r, F.r2, F.p0, F.p1, partials_.get(), state_, tiles1_for(w_sweep_next()), s,
-                   part, w_sweep_next(), spec_.sigma);
+                   part, w_sweep_next(), spec_.sigma, shift<T>());
   else
     launch_pcg_a_wave<T>(geom_, tables_, F.r, F.p0, F.p1, halo<T>(), partials_.get(), state_, tiles_, opt_.exact, s);
 }

@@ -62,6 +62,40 @@ k_finite(const double* __restrict__ src, int64_t ld, int rows, int cols, int* fl
   if (bad) *flag = 1;  // every writer stores the same value
 }
 
+// k_scatter for a reaction field: dst = T(sigma + c), the sum in fp64 and rounded once to the storage type
+template <typename T>
+__global__ void __launch_bounds__(kIoCols)
+k_scatter_shift(const double* __restrict__ src, int64_t ld, T* __restrict__ dst, int64_t pitch, int rows, int cols,
+                double sigma) {
+  const int j = blockIdx.x * kIoCols + threadIdx.x;
+  const int i0 = blockIdx.y * kIoRows;
+  if (j >= cols) return;
+  double v[kIoRows] = {};
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u)
+    if (i0 + u < rows) v[u] = src[int64_t(i0 + u) * ld + j];
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u)
+    if (i0 + u < rows)
+      __builtin_nontemporal_store(static_cast<T>(sigma + v[u]), dst + int64_t(i0 + u) * pitch + j);
+}
+
+// k_finite for a reaction field: raises the flag on a NaN, an infinity or a negative value (-0.0 passes)
+__global__ void __launch_bounds__(kIoCols)
+k_reaction_check(const double* __restrict__ src, int64_t ld, int rows, int cols, int* flag) {
+  const int j = blockIdx.x * kIoCols + threadIdx.x;
+  const int i0 = blockIdx.y * kIoRows;
+  if (j >= cols) return;
+  bool bad = false;
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u)
+    if (i0 + u < rows) {
+      const double v = src[int64_t(i0 + u) * ld + j];
+      bad |= !(v >= 0.0) || v == __builtin_huge_val();  // !(v >= 0): a NaN or a negative value
+    }
+  if (bad) *flag = 1;  // every writer stores the same value
+}
+
 // local nodes (li0 .. li0 + rows - 1) x (lj0 .. lj0 + cols - 1) of a subdomain whose local (0, 0) is
 // global (gi0, gj0); w, pa, pb point to local (0, 0)
 template <typename T>
@@ -99,6 +133,21 @@ void launch_scatter(const double* src, int64_t ld, T* dst, int64_t pitch, int ro
 }
 template void launch_scatter<double>(const double*, int64_t, double*, int64_t, int, int, hipStream_t);
 template void launch_scatter<float>(const double*, int64_t, float*, int64_t, int, int, hipStream_t);
+
+template <typename T>
+void launch_scatter_shift(const double* src, int64_t ld, T* dst, int64_t pitch, int rows, int cols, double sigma,
+                          hipStream_t s) {
+  hipLaunchKernelGGL((k_scatter_shift<T>), io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, dst, pitch, rows, cols,
+                     sigma);
+  HIP_CHECK(hipGetLastError());
+}
+template void launch_scatter_shift<double>(const double*, int64_t, double*, int64_t, int, int, double, hipStream_t);
+template void launch_scatter_shift<float>(const double*, int64_t, float*, int64_t, int, int, double, hipStream_t);
+
+void launch_reaction_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s) {
+  hipLaunchKernelGGL(k_reaction_check, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);
+  HIP_CHECK(hipGetLastError());
+}
 
 void launch_finite_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s) {
   hipLaunchKernelGGL(k_finite, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);

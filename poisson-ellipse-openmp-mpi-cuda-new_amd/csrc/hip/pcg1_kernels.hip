@@ -82,8 +82,13 @@ __device__ long long g_wtrace_it = -1;
 //    VGPRs) and fp64 PF 2 (131 free, 128 forced).
 //  * fp32 arithmetic (C = float): the fp32 pipeline needs about half the registers; whatever the
 //    allocator picks at the 4-wave bound of the plain sweep (see kPcg1F32Waves).
+//  * the field sweeps (SH = kShiftField, a session with a reaction field) carry two more rows (the shift of
+//    rows m-1 and m-2) and prefetch one more row per slot: 8 + 4 (PF + 1) VGPRs in fp64 on top of their sigma
+//    twins' 123 (plain) / 163 (w) at PF 1.  Held to the twins' bounds of 128 / 168 they spill (44 / 76 VGPRs,
+//    104 / 124 B of scratch), so they are bounded one class lower -- plain sweeps at 3 waves per SIMD, w sweeps
+//    at 2 -- and compile without scratch (profiles/r11/reaction/).
 template <typename T, typename C, int VEC, int WAVES, int PF, bool WS>
-constexpr int pcg1_min_waves() {
+constexpr int pcg1_min_waves_base() {
   // lockstep workgroups (WAVES 4 / 8, fp64, prefetch 1): the plain sweep at 4 waves per SIMD (2
   // eight-wave or 4 four-wave workgroups per CU), the w sweep at 3 with four-wave workgroups
   if (VEC == 2 && (WAVES == 4 || WAVES == 8) && PF == 1 && std::is_same_v<C, double>)
@@ -93,6 +98,13 @@ constexpr int pcg1_min_waves() {
   if (!WS && (PF == 1 || (sizeof(T) == 4 && PF <= 3) || (sizeof(T) == 8 && PF == 2))) return 4;
   return PF <= 2 ? 3 : 2;  // the w sweeps (triple paths) and fp64 PF 3
 }
+template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int SH = 0>
+constexpr int pcg1_min_waves() {
+  constexpr int base = pcg1_min_waves_base<T, C, VEC, WAVES, PF, WS>();
+  if (SH != 2) return base;
+  // (the fp32-arithmetic w sweeps run at 4: their field twins still spill 2 VGPRs at 3 with prefetch 2)
+  return std::max(1, base - (WS && std::is_same_v<C, float> ? 2 : 1));
+}
 
 // Which tiles a launch covers (launch_pcg1's part) and where tile k of that launch sits.
 struct Pcg1Part {
@@ -101,6 +113,9 @@ struct Pcg1Part {
   const Pcg1Slot* order;  // position -> tile + row classes (pcg1_build_order), or nullptr: pcg1_tile's order
   int count;         // tiles of this launch
   double sigma;      // ProblemSpec::sigma, read by the SH sweeps only (last, after everything a sweep reads)
+  // the subdomain's shift field T(sigma + c) at local (0, 0), in the fields' storage type and layout: read
+  // by the field sweeps (SH = kShiftField) only
+  const void* shift;
 };
 
 // k-th tile of the part -> (ti, tj); false past the end.  The frame is enumerated as: tile rows
@@ -133,9 +148,11 @@ __host__ __device__ inline bool pcg1_tile(int k, const Pcg1Part& P, int tiles_j,
 }
 
 // SH: the sweep of the screened problem (ProblemSpec::sigma != 0; pcg1_march.hpp) -- A + sigma I and
-// D + sigma, sigma from Pcg1Part.  launch_pcg1 picks it; SH = false is the sweep of every other solve.
-template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int DPF = 0, bool SH = false>
-__global__ void __launch_bounds__(64 * WAVES, (pcg1_min_waves<T, C, VEC, WAVES, PF, WS>()))
+// D + sigma, sigma from Pcg1Part.  launch_pcg1 picks it; SH = 0 is the sweep of every other solve.
+// SH = kShiftField (2): the sweep of a session with a reaction field -- the shift of every node from
+// Pcg1Part::shift, loaded with r and p (one more row per fetch, two more carried rows).
+template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int DPF = 0, int SH = kShiftNone>
+__global__ void __launch_bounds__(64 * WAVES, (pcg1_min_waves<T, C, VEC, WAVES, PF, WS, SH>()))
 k_pcg1(DevGeom G, DevTables Tb, T* __restrict__ w, T* r, T* r2, T* p0, T* p1,
        double* __restrict__ partials, PcgState* S, int TI, int tiles_j, int ntiles, Pcg1Part part) {
   constexpr int WO = 64 * VEC - 4;  // owned columns per tile
@@ -187,10 +204,12 @@ k_pcg1(DevGeom G, DevTables Tb, T* __restrict__ w, T* r, T* r2, T* p0, T* p1,
                     G.gj0 + j0 - 2 >= 1 && G.gj0 + j0 + 64 * VEC - 3 <= G.N - 1;
   const bool use_cls = part.order != nullptr && TI + 5 <= 64 / 2;  // 2 bits for each of the TI+5 rows
   const ArithF AF{float(G.cx), float(G.cy), float(G.dinv_in), float(G.dinv_out), float(G.inv_eps),
-                  SH ? float(part.sigma) : 0.0f, SH ? part.sigma : 0.0};
+                  SH == kShiftSigma ? float(part.sigma) : 0.0f, SH == kShiftSigma ? part.sigma : 0.0};
+  [[maybe_unused]] const T* shf = nullptr;
+  if constexpr (SH == kShiftField) shf = static_cast<const T*>(part.shift);
 #define PMX_MARCH(E, F)                                                                                       \
   pcg1_march<T, C, VEC, PF, E, F, 0, (WAVES > 1), SH>(G, Tb, AF, w, rold, rnew, pold, pnew, i0, i1, j0, j1, alpha, \
-                                                    beta, c1, c2, acc, scol, ocls, use_cls)
+                                                    beta, c1, c2, acc, scol, ocls, use_cls, nullptr, shf)
   // LDS-DMA ring of the FAST march (pcg1_march's DPF mode): DPF slots of r, p (, w) rows per wave
   constexpr int kRingDoubles = DPF > 0 ? DPF * (WS ? 3 : 2) * 128 : 2;
   __shared__ double s_ring[WAVES * kRingDoubles];
@@ -468,7 +487,7 @@ int pcg1_build_order(const DevGeom& G, const DevTables& Tb, TileCfg& tc, Pcg1Slo
   std::vector<Pcg1Slot> order(3 * per, Pcg1Slot{-1, 0, 0ull});
   int nslow = 0;
   for (int part = 0; part <= 2; ++part) {
-    const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, nullptr, 0, 0.0};
+    const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, nullptr, 0, 0.0, nullptr};
     const int count = part == 0 ? n : part == 1 ? tc.interior_tiles() : n - tc.interior_tiles();
     // groups: runs of up to gw consecutive tiles of the part's enumeration within one tile row
     std::vector<std::vector<int>> groups;
@@ -577,7 +596,7 @@ int pcg1_lds_pad(int wpcu, int waves) {
 template <typename T>
 void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0, T* p1,
                  double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part, bool wsweep,
-                 double sigma) {
+                 double sigma, const T* shift) {
   PMX_CHECK(tc.kind == 3, "launch_pcg1 needs make_pcg1_tiles");
   PMX_CHECK(part >= 0 && part <= 2, "launch_pcg1: part must be 0, 1 or 2");
   const int tiles = part == 0 ? tc.ntiles() : part == 1 ? tc.interior_tiles() : tc.ntiles() - tc.interior_tiles();
@@ -587,7 +606,7 @@ void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0
   PMX_CHECK(tc.waves == 1 || grouped, "pcg1: workgroups of several waves need the grouped dispatch order");
   const int nb = grouped ? tc.groups[part] : tiles;
   const int count = grouped ? nb * tc.waves : tiles;
-  const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, ord, count, sigma};
+  const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, ord, count, sigma, shift};
   if (tiles == 0) return;
   PMX_CHECK(G.nb == 0 || (G.nx >= 2 && G.ny >= 2), "pcg1 on a decomposed grid needs subdomains >= 2 x 2");
   const int bs = 64 * tc.waves;
@@ -611,35 +630,43 @@ void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0
     PMX_PCG1_CD(C, V, WV, PF, 0);                                                                        \
   } while (0)
   // the screened problem's sweeps (SH): the shapes the library picks on its own -- VEC 2, 1 wave,
-  // register prefetch 1 or 2
-#define PMX_PCG1_SH(C, PF)                                                                               \
+  // register prefetch 1 or 2.  MODE: kShiftSigma, or kShiftField for a session with a reaction field
+  // (its shift field holds sigma + c, so sigma itself is not read)
+#define PMX_PCG1_SH(C, PF, MODE)                                                                         \
   do {                                                                                                   \
     if (wsweep)                                                                                          \
-      hipLaunchKernelGGL((k_pcg1<T, C, 2, 1, PF, true, 0, true>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, \
+      hipLaunchKernelGGL((k_pcg1<T, C, 2, 1, PF, true, 0, MODE>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, \
                          r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);                  \
     else                                                                                                 \
-      hipLaunchKernelGGL((k_pcg1<T, C, 2, 1, PF, false, 0, true>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, \
+      hipLaunchKernelGGL((k_pcg1<T, C, 2, 1, PF, false, 0, MODE>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, \
                          r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);                  \
   } while (0)
-  if (sigma != 0.0) {
+#define PMX_PCG1_SHIFT(MODE)                                                                             \
+  do {                                                                                                   \
+    if (f32) {                                                                                           \
+      if constexpr (std::is_same_v<T, float>) {                                                          \
+        if (tc.pf == 1) PMX_PCG1_SH(float, 1, MODE);                                                     \
+        else PMX_PCG1_SH(float, 2, MODE);                                                                \
+      }                                                                                                  \
+    } else if (tc.pf == 1) {                                                                             \
+      PMX_PCG1_SH(double, 1, MODE);                                                                      \
+    } else {                                                                                             \
+      PMX_PCG1_SH(double, 2, MODE);                                                                      \
+    }                                                                                                    \
+  } while (0)
+  if (sigma != 0.0 || shift) {
     PMX_CHECK(tc.vec == 2 && tc.waves == 1 && (tc.pf == 1 || tc.pf == 2) && tc.dpf == 0,
-              "pcg1 with sigma != 0 runs the default tile shapes (vec 2 x 1 wave, prefetch 1 or 2, no LDS-DMA)");
+              "pcg1 with sigma != 0 or a reaction field runs the default tile shapes (vec 2 x 1 wave, prefetch 1 "
+              "or 2, no LDS-DMA)");
     bool f32 = false;
     if constexpr (std::is_same_v<T, float>) f32 = tc.arith32 != 0;
     PMX_CHECK(!tc.arith32 || f32, "pcg1: fp32 arithmetic needs fp32 storage");
-    if (f32) {
-      if constexpr (std::is_same_v<T, float>) {
-        if (tc.pf == 1) PMX_PCG1_SH(float, 1);
-        else PMX_PCG1_SH(float, 2);
-      }
-    } else if (tc.pf == 1) {
-      PMX_PCG1_SH(double, 1);
-    } else {
-      PMX_PCG1_SH(double, 2);
-    }
+    if (shift) PMX_PCG1_SHIFT(kShiftField);
+    else PMX_PCG1_SHIFT(kShiftSigma);
     HIP_CHECK(hipGetLastError());
     return;
   }
+#undef PMX_PCG1_SHIFT
 #undef PMX_PCG1_SH
   // fp32 arithmetic: fp32 storage only, the default tile shape (VEC 2, 1 wave) and prefetch 1-3
 #define PMX_PCG1(V, WV, PF)                                                                              \
@@ -712,12 +739,13 @@ void* pcg1_wave_trace_setup(long long it, int nwaves) {
 #endif
 
 template void launch_pcg1<double>(const DevGeom&, const DevTables&, double*, double*, double*, double*,
-                                  double*, double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double);
+                                  double*, double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double,
+                                  const double*);
 template void launch_pcg1_halo<double>(const DevGeom&, double*, double*, double*, double*, HaloBufs<double>,
                                         long long, bool, hipStream_t, long long*);
 template void launch_pcg1_halo<float>(const DevGeom&, float*, float*, float*, float*, HaloBufs<float>,
                                        long long, bool, hipStream_t, long long*);
 template void launch_pcg1<float>(const DevGeom&, const DevTables&, float*, float*, float*, float*, float*,
-                                 double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double);
+                                 double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double, const float*);
 
 }  // namespace pmx

@@ -308,10 +308,25 @@ __device__ __forceinline__ void coef_c(const RowCo& c, const DevTables& Tb, cons
 // A x gains + sigma x_centre as one explicit FMA after the unshifted expression, every D gains + sigma; the
 // two precomputed reciprocals of the uniform rows arrive with sigma included.  Nothing else differs, and
 // SH = false is the code of every sweep without it.
-template <typename C, bool SH = false>
-__device__ __forceinline__ C zdiv_c(int ucls, C r, C a0, C a1, C b0, C b1, const DevGeom& G, const ArithF& F) {
-  if constexpr (std::is_same_v<C, double>) {
-    if constexpr (SH) return zdiv_u_sh(ucls, r, a0, a1, b0, b1, G, F.sigma_d);
+//
+// SH is the shift switch: kShiftNone (0), kShiftSigma (1, the constant above) or kShiftField (2) -- the
+// reaction field, s = T(sigma + c) of the node itself (Pcg1Row::s, carried down the pipeline like Pm1 / Pm2)
+// in place of F.sigma.  Its D + s has no precomputed reciprocal: every class divides (zdiv_field, and its
+// fp32 twin here), so all call sites agree bitwise.  States 0 and 1 are the code they were.
+constexpr int kShiftNone = 0, kShiftSigma = 1, kShiftField = 2;
+
+template <typename C, int SH = kShiftNone>
+__device__ __forceinline__ C zdiv_c(int ucls, C r, C a0, C a1, C b0, C b1, const DevGeom& G, const ArithF& F,
+                                    C s = C(0)) {
+  if constexpr (SH == kShiftField) {
+    if constexpr (std::is_same_v<C, double>) {
+      return zdiv_field(r, a0, a1, b0, b1, G, s);
+    } else {
+      const float D = __builtin_fmaf(a1 + a0, F.cx, (b1 + b0) * F.cy);
+      return r / (D + s);
+    }
+  } else if constexpr (std::is_same_v<C, double>) {
+    if constexpr (SH != 0) return zdiv_u_sh(ucls, r, a0, a1, b0, b1, G, F.sigma_d);
     else return zdiv_u<false>(ucls, r, a0, a1, b0, b1, G);
   } else {
     if (ucls == 1) return r * F.dinv_in;
@@ -321,22 +336,24 @@ __device__ __forceinline__ C zdiv_c(int ucls, C r, C a0, C a1, C b0, C b1, const
     if (in) return r * F.dinv_in;
     if (out) return r * F.dinv_out;
     const float D = __builtin_fmaf(a1 + a0, F.cx, (b1 + b0) * F.cy);
-    if constexpr (SH) return r / (D + F.sigma);
+    if constexpr (SH != 0) return r / (D + F.sigma);
     else return r / D;
   }
 }
 
-template <typename C, bool SH = false>
+template <typename C, int SH = kShiftNone>
 __device__ __forceinline__ C apply_c(C pc, C pim, C pip, C pjm, C pjp, C a0, C a1, C b0, C b1, const DevGeom& G,
-                                     const ArithF& F) {
+                                     const ArithF& F, C s = C(0)) {
   if constexpr (std::is_same_v<C, double>) {
-    if constexpr (SH) return apply_a_sh<false>(pc, pim, pip, pjm, pjp, a0, a1, b0, b1, G, F.sigma_d);
+    if constexpr (SH == kShiftField) return apply_a_sh<false>(pc, pim, pip, pjm, pjp, a0, a1, b0, b1, G, s);
+    else if constexpr (SH != 0) return apply_a_sh<false>(pc, pim, pip, pjm, pjp, a0, a1, b0, b1, G, F.sigma_d);
     else return apply_a<false>(pc, pim, pip, pjm, pjp, a0, a1, b0, b1, G);
   } else {
     const float x = __builtin_fmaf(a1, pc - pip, a0 * (pc - pim));
     const float y = __builtin_fmaf(b1, pc - pjp, b0 * (pc - pjm));
     const float Ap = __builtin_fmaf(F.cx, x, F.cy * y);
-    if constexpr (SH) return __builtin_fmaf(F.sigma, pc, Ap);
+    if constexpr (SH == kShiftField) return __builtin_fmaf(s, pc, Ap);
+    else if constexpr (SH != 0) return __builtin_fmaf(F.sigma, pc, Ap);
     else return Ap;
   }
 }
@@ -344,10 +361,12 @@ __device__ __forceinline__ C apply_c(C pc, C pim, C pip, C pjm, C pjp, C a0, C a
 // A x on the VEC columns of a lane: centre xc, rows i-1 / i+1 xim / xip, the lane neighbours'
 // edge columns left / right (DPP).  fp32 with VEC = 2: both columns in packed fp32 (v_pk_*), the
 // same per-column fmaf sequence as apply_c (bit-identical results).
-template <typename C, int VEC, bool SH = false>
+// s: the row's shift values (kShiftField only).
+template <typename C, int VEC, int SH = kShiftNone>
 __device__ __forceinline__ void apply_row(const C (&xc)[VEC], const C (&xim)[VEC], const C (&xip)[VEC], C left,
                                           C right, const C (&a0)[VEC], const C (&a1)[VEC], const C (&b0)[VEC],
-                                          const C (&b1)[VEC], const DevGeom& G, const ArithF& F, C (&out)[VEC]) {
+                                          const C (&b1)[VEC], const DevGeom& G, const ArithF& F, C (&out)[VEC],
+                                          const C* s = nullptr) {
   if constexpr (std::is_same_v<C, float> && VEC == 2) {
     typedef float f2 __attribute__((ext_vector_type(2)));
     const f2 pc = {xc[0], xc[1]}, pim = {xim[0], xim[1]}, pip = {xip[0], xip[1]};
@@ -357,7 +376,10 @@ __device__ __forceinline__ void apply_row(const C (&xc)[VEC], const C (&xim)[VEC
     const f2 y = __builtin_elementwise_fma(B1, pc - pjp, B0 * (pc - pjm));
     const f2 cx = {F.cx, F.cx}, cy = {F.cy, F.cy};
     f2 r = __builtin_elementwise_fma(cx, x, cy * y);
-    if constexpr (SH) {
+    if constexpr (SH == kShiftField) {
+      const f2 sg = {s[0], s[1]};
+      r = __builtin_elementwise_fma(sg, pc, r);
+    } else if constexpr (SH != 0) {
       const f2 sg = {F.sigma, F.sigma};
       r = __builtin_elementwise_fma(sg, pc, r);
     }
@@ -367,7 +389,7 @@ __device__ __forceinline__ void apply_row(const C (&xc)[VEC], const C (&xim)[VEC
 #pragma unroll
     for (int u = 0; u < VEC; ++u)
       out[u] = apply_c<C, SH>(xc[u], xim[u], xip[u], u == 0 ? left : xc[u - 1], u == VEC - 1 ? right : xc[u + 1],
-                              a0[u], a1[u], b0[u], b1[u], G, F);
+                              a0[u], a1[u], b0[u], b1[u], G, F, SH == kShiftField ? s[u] : C(0));
   }
 }
 
@@ -400,9 +422,13 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
 }
 
-template <typename T, int VEC>
+template <typename T, int VEC, bool FLD = false>
 struct Pcg1Row {
   T r[VEC], p[VEC], w[VEC], q[VEC];  // q: p^{k-2} (WM 3 only)
+};
+template <typename T, int VEC>
+struct Pcg1Row<T, VEC, true> {  // kShiftField: + the row's shift values T(sigma + c)
+  T r[VEC], p[VEC], w[VEC], q[VEC], s[VEC];
 };
 
 // w schedule of one sweep (template WM of pcg1_march): 0 = w untouched; 1 = pairs, w += c1 p^{k-1}
@@ -435,15 +461,20 @@ struct Pcg1Row {
 // pieces at different times (bench/probe/dma_march.hip k_lock: 16384^2, 16 waves per CU, 1.846 ->
 // 1.688 ms per sweep).  Pure pacing: no data passes between the waves, every wave of a workgroup
 // marches the same number of rows (one tile row), and a wave that has left no longer counts.
-template <typename T, typename C, int VEC, int PF, int WM, bool FAST, int DPF = 0, bool LOCK = false, bool SH = false>
+template <typename T, typename C, int VEC, int PF, int WM, bool FAST, int DPF = 0, bool LOCK = false,
+          int SH = kShiftNone>
 __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb, const ArithF& F, T* __restrict__ w,
                                            const T* __restrict__ rold, T* __restrict__ rnew,
                                            const T* __restrict__ pold,
                                            T* pnew, int i0, int i1, int j0, int j1,
                                            double alpha_d, double beta_d, double c1_d, double c2_d,
                                            double (&acc)[kNq], double* __restrict__ scol,
-                                           unsigned long long cls, bool use_cls, double* dring = nullptr) {
+                                           unsigned long long cls, bool use_cls, double* dring = nullptr,
+                                           const T* __restrict__ shf = nullptr) {
   constexpr bool WUP = WM != 0;
+  constexpr bool FLD = SH == kShiftField;  // shf: the subdomain's shift field at local (0, 0), r's layout
+  static_assert(!FLD || DPF == 0, "the reaction field runs the register-prefetch march");
+  using Row = Pcg1Row<T, VEC, FLD>;
   static_assert(DPF == 0 || (FAST && VEC == 2 && sizeof(T) == 8 && WM <= 2), "LDS-DMA march: fp64 FAST tiles, WM 0-2");
   constexpr bool PK = std::is_same_v<C, float> && VEC == 2;  // packed fp32 stencils (apply_row)
   const C alpha = C(alpha_d), beta = C(beta_d), c1 = C(c1_d), c2 = C(c2_d);
@@ -480,10 +511,11 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
     coef_c<C>(c, Tb, G, F, scol, u, lane, gj[u], a0, a1, b0, b1);
   };
 
-  auto fetch = [&](int m, Pcg1Row<T, VEC>& b) {
+  auto fetch = [&](int m, Row& b) {
     const int mc = min(max(m, -1), G.nx + 2);  // rows -1 .. nx+2 exist (2 ghost layers)
     load_cols<T, VEC>(rold + int64_t(mc) * P, c0, cmax, b.r);
     load_cols<T, VEC>(pold + int64_t(mc) * P, c0, cmax, b.p);
+    if constexpr (FLD) load_cols<T, VEC>(shf + int64_t(mc) * P, c0, cmax, b.s);
     if constexpr (WUP) {  // w of the row stage B handles next step
       const int wc = min(max(m - 1, -1), G.nx + 2);
       load_cols<T, VEC>(w + int64_t(wc) * P, c0, cmax, b.w);
@@ -497,6 +529,10 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
   C Pm2[VEC], Pm1[VEC], Zm3[VEC], Zm2[VEC], ro1[VEC], po1[VEC], po2[VEC];
 #pragma unroll
   for (int u = 0; u < VEC; ++u) Pm2[u] = Pm1[u] = Zm3[u] = Zm2[u] = ro1[u] = po1[u] = po2[u] = C(0);
+  // kShiftField: the shift values of rows m-1 (stage B) and m-2 (stage C); unused otherwise
+  [[maybe_unused]] C Sm1[VEC], Sm2[VEC];
+#pragma unroll
+  for (int u = 0; u < VEC; ++u) Sm1[u] = Sm2[u] = C(0);
   RowCo cB = row_of(i0 - 3);  // rows m-1, m-2
   RowCo cC = cB;
   bool parked = false;  // column constants in LDS (see col_lds)
@@ -515,20 +551,23 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
 
   const int mfirst = i0 - 2, mlast = i1 + 2;
   // one row step of the 3-stage pipeline on row m's loaded values
-  auto core = [&](int m, const Pcg1Row<T, VEC>& cur) {
+  auto core = [&](int m, const Row& cur) {
     // ---- stage A: p^k of row m
     const bool rowA = FAST || interior_row(m);
     const RowCo cA = row_of(m);
     if (cA.ucls == 0 && !parked) park_cols();
     C Pm[VEC], rom[VEC], pom[VEC];
+    [[maybe_unused]] C sm[VEC];
 #pragma unroll
     for (int u = 0; u < VEC; ++u) {
+      if constexpr (FLD) sm[u] = C(cur.s[u]);
+      else sm[u] = C(0);
       const bool in = FAST || (rowA && colin[u]);
       rom[u] = in ? C(cur.r[u]) : C(0);
       pom[u] = in ? C(cur.p[u]) : C(0);
       C a0, a1, b0, b1;
       coef_c<C>(cA, Tb, G, F, scol, u, lane, gj[u], a0, a1, b0, b1);
-      const C z = zdiv_c<C, SH>(cA.ucls, rom[u], a0, a1, b0, b1, G, F);
+      const C z = zdiv_c<C, SH>(cA.ucls, rom[u], a0, a1, b0, b1, G, F, sm[u]);
       const C v = fma_c(beta, pom[u], z);
       Pm[u] = in ? C(static_cast<T>(v)) : C(0);  // the stored (rounded) p^k is the one used
     }
@@ -553,33 +592,33 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       if constexpr (PK) {
 #pragma unroll
         for (int u = 0; u < VEC; ++u) coef_at(cB, mb, u, a0[u], a1[u], b0[u], b1[u]);
-        apply_row<C, VEC, SH>(Pm1, Pm2, Pm, left, right, a0, a1, b0, b1, G, F, Ap);
+        apply_row<C, VEC, SH>(Pm1, Pm2, Pm, left, right, a0, a1, b0, b1, G, F, Ap, Sm1);
         // p^{k-2} recovery (WM 2): A p^{k-1}
         if constexpr (WM == 2)
-          apply_row<C, VEC, SH>(po1, po2, pom, oleft, oright, a0, a1, b0, b1, G, F, Apo);
+          apply_row<C, VEC, SH>(po1, po2, pom, oleft, oright, a0, a1, b0, b1, G, F, Apo, Sm1);
       }
 #pragma unroll
       for (int u = 0; u < VEC; ++u) {
         if constexpr (!PK) {
           coef_at(cB, mb, u, a0[u], a1[u], b0[u], b1[u]);
           Ap[u] = apply_c<C, SH>(Pm1[u], Pm2[u], Pm[u], u == 0 ? left : Pm1[u - 1],
-                             u == VEC - 1 ? right : Pm1[u + 1], a0[u], a1[u], b0[u], b1[u], G, F);
+                             u == VEC - 1 ? right : Pm1[u + 1], a0[u], a1[u], b0[u], b1[u], G, F, Sm1[u]);
           if constexpr (WM == 2)
             Apo[u] = apply_c<C, SH>(po1[u], po2[u], pom[u],
                                 u == 0 ? oleft : po1[u - 1], u == VEC - 1 ? oright : po1[u + 1], a0[u], a1[u], b0[u],
-                                b1[u], G, F);
+                                b1[u], G, F, Sm1[u]);
         }
         const bool in = FAST || (rowB && colin[u]);
         const C rn = C(static_cast<T>(fma_c(-alpha, Ap[u], ro1[u])));  // = upd_r<false>
         rs[u] = static_cast<T>(in ? rn : C(0));
-        const C zn = zdiv_c<C, SH>(cB.ucls, rn, a0[u], a1[u], b0[u], b1[u], G, F);
+        const C zn = zdiv_c<C, SH>(cB.ucls, rn, a0[u], a1[u], b0[u], b1[u], G, F, Sm1[u]);
         Zm1[u] = in ? zn : C(0);
         ps[u] = static_cast<T>(Pm1[u]);
         if constexpr (WM == 1) {
           ws[u] = static_cast<T>(fma_c(alpha, Pm1[u], fma_c(c1, po1[u], C(cur.w[u]))));
         } else if constexpr (WM == 2) {
           // r^{k-2} = r^{k-1} + alpha_{k-1} A p^{k-1};  p^{k-2} = (p^{k-1} - D^-1 r^{k-2}) / beta_{k-1}
-          const C zo = zdiv_c<C, SH>(cB.ucls, fma_c(c1, Apo[u], ro1[u]), a0[u], a1[u], b0[u], b1[u], G, F);
+          const C zo = zdiv_c<C, SH>(cB.ucls, fma_c(c1, Apo[u], ro1[u]), a0[u], a1[u], b0[u], b1[u], G, F, Sm1[u]);
           const C t = fma_c(c2, po1[u] - zo, C(cur.w[u]));
           ws[u] = static_cast<T>(fma_c(alpha, Pm1[u], fma_c(c1, po1[u], t)));
         } else if constexpr (WM == 3) {
@@ -608,14 +647,14 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       if constexpr (PK) {
 #pragma unroll
         for (int u = 0; u < VEC; ++u) coef_at(cC, mcr, u, a0[u], a1[u], b0[u], b1[u]);
-        apply_row<C, VEC, SH>(Zm2, Zm3, Zm1, left, right, a0, a1, b0, b1, G, F, Az);
+        apply_row<C, VEC, SH>(Zm2, Zm3, Zm1, left, right, a0, a1, b0, b1, G, F, Az, Sm2);
       }
 #pragma unroll
       for (int u = 0; u < VEC; ++u) {
         if constexpr (!PK) {
           coef_at(cC, mcr, u, a0[u], a1[u], b0[u], b1[u]);
           Az[u] = apply_c<C, SH>(Zm2[u], Zm3[u], Zm1[u], u == 0 ? left : Zm2[u - 1],
-                             u == VEC - 1 ? right : Zm2[u + 1], a0[u], a1[u], b0[u], b1[u], G, F);
+                             u == VEC - 1 ? right : Zm2[u + 1], a0[u], a1[u], b0[u], b1[u], G, F, Sm2[u]);
         }
         if (FAST || own[u]) {
           acc[1] += double(Az[u]) * double(Zm2[u]);
@@ -631,6 +670,10 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       ro1[u] = rom[u];
       if constexpr (WM == 2) po2[u] = po1[u];
       po1[u] = pom[u];
+      if constexpr (FLD) {
+        Sm2[u] = Sm1[u];
+        Sm1[u] = sm[u];
+      }
     }
     cC = cB;
     cB = cA;
@@ -659,7 +702,7 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       constexpr int KS = decltype(ks)::value;
       wait_vmcnt<(DPF - 1) * ND + KS * NS>();
       const double* sl = dring + slot * (ND * 128);
-      Pcg1Row<T, VEC> cur;
+      Row cur;
       const d2 rv = *reinterpret_cast<const d2*>(sl + 2 * lane);
       const d2 pv = *reinterpret_cast<const d2*>(sl + 128 + 2 * lane);
       cur.r[0] = rv.x; cur.r[1] = rv.y;
@@ -688,7 +731,7 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
   } else {
     // ring of PF + 1 row buffers, unrolled by its size so no buffer is ever copied: step m reads
     // slot q and refills the slot step m - 1 consumed
-    Pcg1Row<T, VEC> buf[PF + 1];
+    Row buf[PF + 1];
 #pragma unroll
     for (int q = 0; q < PF; ++q) fetch(min(mfirst + q, mlast), buf[q]);
     bool more = true;

@@ -208,6 +208,20 @@ __device__ __forceinline__ double zdiv_u_sh(int ucls, double r, double a0, doubl
   return r / add_sigma(diag<false>(a0, a1, b0, b1, G), sigma);
 }
 
+// The reaction field (a session's `reaction`; the field state of the shift switch in k_pcg1 / k_init /
+// k_apply): s = T(sigma + c) per node, read from the subdomain's shift field.  A x gains fma(s, x, .) as
+// apply_a_sh does; D + s cannot use a precomputed reciprocal, so EVERY class divides by the one expression
+// below -- the uniform rows form D_u from their class coefficient with make_dev_geom's expression (before
+// it adds sigma; here with one explicit FMA) -- and every call site (march stages A and B, the p^{k-2}
+// recovery) agrees bitwise.
+__device__ __forceinline__ double diag_field(double a0, double a1, double b0, double b1, const DevGeom& G, double s) {
+  return add_sigma(__builtin_fma(a1 + a0, G.cx, (b1 + b0) * G.cy), s);
+}
+__device__ __forceinline__ double zdiv_field(double r, double a0, double a1, double b0, double b1, const DevGeom& G,
+                                             double s) {
+  return r / diag_field(a0, a1, b0, b1, G, s);
+}
+
 // w + alpha p and r - alpha A p.  EXACT: the reference's separate multiply and add
 // (stage0/Withoutopenmp1.cpp:135-143); fast: one explicit FMA each, so the r values packed for the
 // halo by k_edge_r equal those k_pcg_b stores.

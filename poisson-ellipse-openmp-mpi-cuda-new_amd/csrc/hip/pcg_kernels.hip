@@ -55,13 +55,15 @@ TileCfg make_tiles(const DevGeom& G, int block, int rows) {
 // neighbours by plain loads.
 // SH: the screened problem (ProblemSpec::sigma != 0): A w + sigma w in the residual, D + sigma in the
 // (z0, r0) partial, in every mode; sigma is InitData's last member, and the launchers pick SH from it.
+// SH = 2 (a session with a reaction field): the node's own shift T(sigma + c) from X.shift -- the
+// subdomain's shift field, r's layout -- in place of X.sigma, in the same two places and in rho_B.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double resid(double B, double Aw) {
   PMX_NO_CONTRACT
   return B - Aw;
 }
 
-template <typename T, int BLOCK, int MODE, bool SH = false>
+template <typename T, int BLOCK, int MODE, int SH = 0>
 __global__ void __launch_bounds__(BLOCK)
 k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T> H,
        double* __restrict__ partials, int TI, int tiles_j, InitData<T> X) {
@@ -97,6 +99,8 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
       const double a0 = face_a(cc, rc.rv0, G), a1 = face_a(cc, rc.rv1, G);
       const double b0 = face_b(rc, cc.rh0, G), b1 = face_b(rc, cc.rh1, G);
       const int64_t c = int64_t(i) * P + j;
+      [[maybe_unused]] double sg = X.sigma;
+      if constexpr (SH == 2) sg = double(X.shift[c]);
       // B_ij = F inside D (stage0/Withoutopenmp1.cpp:60)
       const bool in = geo::inside(Tb.x[gi], yj, G.ax, G.by, G.ref_ellipse != 0);
       T Bs;
@@ -111,7 +115,7 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
         const double wp = gi + 1 >= G.M ? 0.0 : wl(c + P);
         const double wjm = djm ? 0.0 : wl(c - 1), wjp = djp ? 0.0 : wl(c + 1);
         double Aw = apply_a<true>(wc, wm, wp, wjm, wjp, a0, a1, b0, b1, G);
-        if constexpr (SH) Aw = __builtin_fma(X.sigma, wc, Aw);  // as apply_a_sh
+        if constexpr (SH != 0) Aw = __builtin_fma(sg, wc, Aw);  // as apply_a_sh
         const double e = resid(Bq, Aw);
         acc = __builtin_fma(e, e, acc);
         wm = wc;
@@ -122,14 +126,14 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
           const double wp = gi + 1 >= G.M ? 0.0 : wl(c + P);
           const double wjm = djm ? 0.0 : wl(c - 1), wjp = djp ? 0.0 : wl(c + 1);
           double Aw = apply_a<true>(wc, wm, wp, wjm, wjp, a0, a1, b0, b1, G);
-          if constexpr (SH) Aw = __builtin_fma(X.sigma, wc, Aw);  // as apply_a_sh
+          if constexpr (SH != 0) Aw = __builtin_fma(sg, wc, Aw);  // as apply_a_sh
           rs = static_cast<T>(resid(Bq, Aw));
           wm = wc;
           wc = wp;
         }
         const double rq = static_cast<double>(rs);
         double D = diag<true>(a0, a1, b0, b1, G);
-        if constexpr (SH) D = add_sigma(D, X.sigma);
+        if constexpr (SH != 0) D = add_sigma(D, sg);
         const double z = (D != 0.0) ? rq / D : 0.0;
         acc += z * rq;
         if (MODE == kInitData && X.rho_b) accb += ((D != 0.0) ? Bq / D : 0.0) * Bq;  // rho_B's partial
@@ -284,12 +288,18 @@ __global__ void k_local_allreduce(double* const* bufs, int nranks, int nq) {
 
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
-                 double* partials, const TileCfg& tc, hipStream_t s, double sigma) {
-  if (sigma != 0.0) {
+                 double* partials, const TileCfg& tc, hipStream_t s, double sigma, const T* shift) {
+  if (shift) {
+    InitData<T> X;
+    X.shift = shift;
+    PMX_BLOCK_DISPATCH(tc.block,
+        hipLaunchKernelGGL((k_init<T, B, kInitPlain, 2>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
+                           partials, tc.rows, tc.tiles_j, X));
+  } else if (sigma != 0.0) {
     InitData<T> X;
     X.sigma = sigma;
     PMX_BLOCK_DISPATCH(tc.block,
-        hipLaunchKernelGGL((k_init<T, B, kInitPlain, true>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
+        hipLaunchKernelGGL((k_init<T, B, kInitPlain, 1>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
                            partials, tc.rows, tc.tiles_j, X));
   } else {
     PMX_BLOCK_DISPATCH(tc.block,
@@ -309,14 +319,20 @@ void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBuf
                       const TileCfg& tc, const InitData<T>& X, bool measure, hipStream_t s) {
   PMX_CHECK(tc.block == 256, "the data init runs the init tiling (256 columns per tile)");
   const bool sh = X.sigma != 0.0;
-  if (measure && sh)
-    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, true>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+  if (measure && X.shift)
+    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, 2>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+                       partials, tc.rows, tc.tiles_j, X);
+  else if (X.shift)
+    hipLaunchKernelGGL((k_init<T, 256, kInitData, 2>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+                       partials, tc.rows, tc.tiles_j, X);
+  else if (measure && sh)
+    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, 1>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
                        partials, tc.rows, tc.tiles_j, X);
   else if (measure)
     hipLaunchKernelGGL((k_init<T, 256, kInitMeasure>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
                        partials, tc.rows, tc.tiles_j, X);
   else if (sh)
-    hipLaunchKernelGGL((k_init<T, 256, kInitData, true>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+    hipLaunchKernelGGL((k_init<T, 256, kInitData, 1>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
                        partials, tc.rows, tc.tiles_j, X);
   else
     hipLaunchKernelGGL((k_init<T, 256, kInitData>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
@@ -354,7 +370,7 @@ void launch_local_allreduce(double* const* bufs, int nranks, int nq, hipStream_t
 
 #define PMX_INST(T)                                                                              \
   template void launch_init<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>, double*,  \
-                               const TileCfg&, hipStream_t, double);                             \
+                               const TileCfg&, hipStream_t, double, const T*);                   \
   template void launch_init_data<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>,       \
                                     double*, const TileCfg&, const InitData<T>&, bool,           \
                                     hipStream_t);                                                 \

@@ -41,8 +41,20 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
   GpuOptions pre = cfg_.opt;
   // a multi-process RCCL run tracks device progress for its hang watchdog (GpuOptions::progress)
   if ((cfg_.comm == CommKind::kRccl || cfg_.comm == CommKind::kIpc) && cfg_.world > 1) pre.progress = 1;
+  UserField react(cfg_.reaction);
+  react.ld = cfg_.reaction_ld;
+  react.on_device = cfg_.reaction_on_device;
+  react.stream = cfg_.reaction_stream;
+  if (react) {
+    if (cfg_.comm != CommKind::kSelf && cfg_.comm != CommKind::kLocal)
+      throw std::invalid_argument("a reaction field needs a session that owns every subdomain (world 1 or the "
+                                  "local communicator); multi-process transports are not supported");
+    pre.reaction = 1;
+  }
   GpuOptions base = resolve_options(pre);
-  apply_sigma_rules(cfg_.spec, pg_, base);  // sigma != 0: pcg1 on the row march, or std::invalid_argument
+  // sigma != 0 or a reaction field: pcg1 on the row march, or std::invalid_argument
+  apply_sigma_rules(cfg_.spec, pg_, base);
+  if (react) check_reaction(react);  // before anything is allocated
   if (base.algo == -1) {
     HIP_CHECK(hipSetDevice(cfg_.devices[0]));
     size_t free_b = 0, total_b = 0;
@@ -60,6 +72,7 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
     const Subdomain sd = decompose_2d(cfg_.spec.M, cfg_.spec.N, pg_, cfg_.ranks[i]);
     solvers_.push_back(std::make_unique<GpuSubdomainSolver>(cfg_.spec, sd, o));
   }
+  if (react) upload_reaction(react);
   if (!cfg_.defer_connect) connect();
 }
 
@@ -188,7 +201,66 @@ bool Session::direct_rows() const {
 
 void Session::progress(int i, long long out[3]) const { solvers_.at(size_t(i))->progress(out); }
 
+void Session::check_reaction(const UserField& c) const {
+  const int M = cfg_.spec.M, N = cfg_.spec.N;
+  const int64_t ld = c.ld ? c.ld : N + 1;
+  if (ld < N + 1) throw std::invalid_argument("reaction: row stride below N + 1");
+  bool bad = false;
+  if (c.on_device) {
+    for (int d : cfg_.devices)
+      if (d != cfg_.devices[0])
+        throw std::invalid_argument("a device reaction field needs every subdomain of the session on its device");
+    HIP_CHECK(hipSetDevice(cfg_.devices[0]));
+    int* flag = nullptr;  // for the call only
+    int h = 0;
+    HIP_CHECK(hipMalloc(&flag, sizeof(int)));
+    try {
+      HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), c.stream));
+      launch_reaction_check(c.ptr + ld + 1, ld, M - 1, N - 1, flag, c.stream);  // the interior nodes only
+      HIP_CHECK(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+      HIP_CHECK(hipStreamSynchronize(c.stream));
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);
+      (void)hipFree(flag);
+      throw;
+    }
+    HIP_CHECK(hipFree(flag));
+    bad = h != 0;
+  } else {
+    for (int i = 1; i <= M - 1 && !bad; ++i)
+      for (int j = 1; j <= N - 1; ++j) {
+        const double v = c.ptr[int64_t(i) * ld + j];
+        if (!(v >= 0.0) || std::isinf(v)) {
+          bad = true;
+          break;
+        }
+      }
+  }
+  if (bad) throw std::invalid_argument("reaction must be finite and >= 0 on every interior node");
+}
+
+void Session::upload_reaction(const UserField& c) {
+  const int64_t ld = c.ld ? c.ld : cfg_.spec.N + 1;
+  // a device field on its producer's stream (ordered after its producer, no event needed); every solver
+  // returns once that stream has consumed the field
+  for (auto& sp : solvers_) sp->set_reaction(c.ptr, ld, c.on_device, c.on_device ? c.stream : nullptr);
+}
+
+void Session::set_reaction(const UserField& c) {
+  if (!has_reaction())
+    throw std::invalid_argument("set_reaction needs a session built with a reaction field (make_session(p, "
+                                "reaction=c)): sessions without one hold no shift field");
+  if (!c) throw std::invalid_argument("set_reaction: no field given");
+  check_reaction(c);
+  if (!drivers_.empty()) synchronize();  // no sweep in flight reads the field
+  upload_reaction(c);
+  stale_ = true;
+}
+
 ErrorStats Session::error_norms() {
+  if (has_reaction())
+    throw std::invalid_argument("error_norms: the closed-form solution does not solve a problem with a reaction "
+                                "field; compare the solution with your own (PoissonEllipse.error_norms(w, exact=u))");
   if (cfg_.spec.sigma != 0.0)
     throw std::invalid_argument("error_norms: the closed-form solution holds for sigma = 0 only; compare the "
                                 "solution with your own (PoissonEllipse.error_norms(w, exact=u))");
@@ -205,6 +277,7 @@ ErrorStats Session::error_norms() {
 }
 
 void Session::init() {
+  stale_ = false;
   for_drivers([](size_t, PcgDriver& d) { d.init(); });
 }
 
@@ -373,6 +446,13 @@ void Session::apply_device(const UserField& x, const UserField& out, const UserF
   K.alpha = alpha; K.beta = beta; K.gamma = y ? gamma : 0.0; K.c0 = c0; K.sigma = cfg_.spec.sigma;
   K.plain = alpha == 1.0 && beta == 0.0 && !y && c0 == 0.0;
   for (size_t i = 0; i < solvers_.size(); ++i) {
+    if (has_reaction()) {  // the owning subdomain's shift field, in sigma's place
+      K.shift = solvers_[i]->shift_base();
+      K.spitch = solvers_[i]->pitch();
+      K.sgi0 = solvers_[i]->sd().gi0();
+      K.sgj0 = solvers_[i]->sd().gj0();
+      K.selem = int(solvers_[i]->elem_bytes());
+    }
     // the owned nodes, widened by the global boundary row / column where the block touches it (as k_gather)
     const Subdomain& sd = solvers_[i]->sd();
     const int i0 = sd.gi0() == 0 ? 0 : sd.gi0() + 1, i1 = sd.gi0() + sd.nx + 1 == M ? M : sd.gi0() + sd.nx;
@@ -384,6 +464,7 @@ void Session::apply_device(const UserField& x, const UserField& out, const UserF
 }
 
 void Session::step(int64_t n) {
+  PMX_CHECK(!stale_, "step: the reaction field changed (set_reaction) since the last init; call init() or solve()");
   for_drivers([n](size_t, PcgDriver& d) { d.enqueue_iterations(n); });
 }
 
@@ -400,6 +481,8 @@ RunStats Session::solve_impl(int poll_batches, bool do_init, int64_t every, cons
   // every rank's driver iterates to the same device stop decision (the all-reduced scalars are
   // identical everywhere); rank 0's statistics are returned
   std::vector<RunStats> st(drivers_.size());
+  if (do_init) stale_ = false;
+  PMX_CHECK(!stale_, "the reaction field changed (set_reaction) since the last init; call init() or solve()");
   for_drivers([&](size_t i, PcgDriver& d) {
     std::function<void(const PcgState&)> cb;
     if (every > 0 && !save_path.empty()) {
@@ -473,6 +556,9 @@ std::vector<double> Session::gather_local_w() {
 }
 
 void Session::require_no_sigma(const char* what) const {
+  if (has_reaction())
+    throw std::invalid_argument(std::string(what) + ": checkpoint files do not record a reaction field (format "
+                                "v7); sessions with one cannot be checkpointed");
   if (cfg_.spec.sigma != 0.0)
     throw std::invalid_argument(std::string(what) + ": checkpoint files do not record sigma (format v7); "
                                 "sessions with sigma != 0 cannot be checkpointed");

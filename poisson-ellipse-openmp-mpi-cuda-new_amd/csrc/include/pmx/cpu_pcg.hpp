@@ -34,8 +34,11 @@ struct SolveResult {
 // rhs / w0: optional global (M+1) x (N+1) row-major arrays.  rhs replaces the constant F as
 // right-hand side under the ellipse mask (B = rhs inside D, 0 elsewhere; boundary nodes ignored),
 // w0 the zero initial iterate (its boundary nodes count as 0): r^0 = B - A w0 in mat_A's arithmetic.
+// reaction: optional global field c(x, y) >= 0 next to spec.sigma: the operator is A + (sigma + c) I and the
+// Jacobi diagonal D + sigma + c on every interior node (boundary values are not read).  The shift enters
+// through the one expression sigma uses, so a constant field equals the sigma solve bitwise.
 SolveResult cpu_solve(const ProblemSpec& spec, int threads = 1, bool keep_solution = true,
-                      const double* rhs = nullptr, const double* w0 = nullptr);
+                      const double* rhs = nullptr, const double* w0 = nullptr, const double* reaction = nullptr);
 
 // Assemble the reference's 2D arrays on the host (tests: kernel bit-equality).
 // a, b are (M+2) x (N+2) including ghost nodes; B is (M+1) x (N+1).
@@ -47,15 +50,16 @@ void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<d
 // matrix on the whole box, no ellipse mask -- in cpu_solve's mat_A arithmetic.  Boundary values of x count as 0
 // and are not read; y may be null (no y term).  Combination order: v = alpha Lx; v = fma(beta, x, v);
 // v = fma(gamma, y, v) with y; v += c0 -- and Lx itself for alpha = 1, beta = 0, no y, c0 = 0.
+// reaction: as cpu_solve (L = A + (sigma + c) I).
 std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const double* y = nullptr, double alpha = 1.0,
-                              double beta = 0.0, double gamma = 1.0, double c0 = 0.0);
+                              double beta = 0.0, double gamma = 1.0, double c0 = 0.0, const double* reaction = nullptr);
 
 // One rank's block (local arrays (nx+2) x (ny+2), row-major, pitch ny+2).
 class CpuSubdomain {
  public:
-  // rhs / w0: as cpu_solve (global arrays; this block, and for w0 its ring, are copied)
+  // rhs / w0 / reaction: as cpu_solve (global arrays; this block, and for w0 its ring, are copied)
   CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads, const double* rhs = nullptr,
-               const double* w0 = nullptr);
+               const double* w0 = nullptr, const double* reaction = nullptr);
 
   const Subdomain& sd() const { return sd_; }
   int pitch() const { return sd_.ny + 2; }
@@ -85,6 +89,7 @@ class CpuSubdomain {
   int threads_;
   std::vector<double> a_, b_, B_, w_, r_, z_, p_, Ap_;
   std::vector<double> w0_;  // initial iterate with its ring (empty: zero)
+  std::vector<double> sh_;  // sigma + c on the owned nodes (empty: no reaction field, the shift is spec.sigma)
 };
 
 // In-process multi-subdomain driver: P subdomains stepped in lock-step with a
@@ -92,7 +97,8 @@ class CpuSubdomain {
 // decomposition + halo logic without MPI (SURVEY §4.2 'distributed (fake)').
 SolveResult cpu_solve_decomposed(const ProblemSpec& spec, int nranks, Split split,
                                  int threads_per_rank = 1, bool keep_solution = true,
-                                 const double* rhs = nullptr, const double* w0 = nullptr);
+                                 const double* rhs = nullptr, const double* w0 = nullptr,
+                                 const double* reaction = nullptr);
 
 // Generic lock-step PCG over CpuSubdomains with pluggable collectives.  The MPI
 // app supplies MPI-backed callbacks; the in-process driver supplies local ones.

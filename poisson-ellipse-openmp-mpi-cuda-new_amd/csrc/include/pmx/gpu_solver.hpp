@@ -169,6 +169,10 @@ struct GpuOptions {
   // which probed block to keep: 0 the fastest (default), 1 the slowest -- for slow-class A/Bs and
   // counter tables on one box (PMX_PLACEMENT_PICK=slowest)
   int placement_pick = 0;
+  // The session solves with a reaction field c(x, y) (Session's `reaction`): every solver allocates the shift
+  // field T(sigma + c) (MemoryPlan::nshift) and runs the field state of the shift switch, under the rules of
+  // the screened problem (apply_sigma_rules).  Set by the Session; the values arrive through set_reaction.
+  int reaction = 0;
   bool resolved = false;  // environment overrides already applied (resolve_options)
 };
 
@@ -200,6 +204,7 @@ constexpr int64_t kCaAutoPoints = 6000000;
 // The screened problem (ProblemSpec::sigma != 0) runs pcg1 on the row march only.  Turns auto choices
 // into that (algo 1 at any grid size, block tiles off) and throws std::invalid_argument, naming the
 // option, for an explicit s-step / pcg2 / exact arithmetic / block tiles.  No-op with sigma == 0.
+// A reaction field (GpuOptions::reaction) falls under the same rules at any sigma.
 // Called before anything is allocated (Session, GpuSubdomainSolver).
 void apply_sigma_rules(const ProblemSpec& spec, const ProcGrid& grid, GpuOptions& resolved);
 int choose_algo(const ProblemSpec& spec, const ProcGrid& grid, const GpuOptions& resolved, double device_total_bytes,
@@ -284,6 +289,19 @@ class GpuSubdomainSolver {
   // every reduction and all-reduce of it.  No-op under the step rule.
   void enqueue_stop_init(hipStream_t s);
   bool has_init_data() const { return !stage_f_.empty() || !stage_w_.empty() || dev_f_ || dev_w_; }
+  // Solvers built with GpuOptions::reaction: (re)fill the shift field with T(sigma + c), rounded once, from
+  // the global (M+1) x (N+1) fp64 array c (row stride ld) -- this subdomain's block with its radius-2 frame,
+  // since decomposed pcg1 recomputes p, A p and z on the ghost diamond; nodes of the box boundary and beyond
+  // are never read and hold 0.  on_device: c is memory of this solver's device, read by the scatter kernel on
+  // s; else a staged host copy goes up with hipMemcpy2DAsync.  Returns after s has consumed c.  The field's
+  // address never changes, so captured graphs stay valid; the values are static, so nothing is exchanged.
+  // The iteration state belongs to the old operator afterwards: the next init starts the new one.
+  void set_reaction(const double* c, int64_t ld, bool on_device, hipStream_t s);
+  bool has_reaction() const { return plan_.nshift != 0; }
+  // the shift field at local (0, 0) in the storage type; nullptr without a reaction field
+  const void* shift_base() const { return plan_.nshift ? field_ptr(plan_.shift_field()) : nullptr; }
+  int64_t pitch() const { return plan_.pitch; }
+  size_t elem_bytes() const { return plan_.elem; }
   // sum over the owned nodes of (B - A w)^2 for the current w (pending steps applied, as
   // download_w), B from `f` (nx x ny, null: the constant F) under the ellipse mask; w's ghost
   // ring counts as zero, so this is the residual of an undecomposed solver.  Synchronous.
@@ -452,6 +470,7 @@ class GpuSubdomainSolver {
     auto at = [&](int f) { return reinterpret_cast<T*>(field_ptr(f)); };
     return {at(0), at(1), plan_.nfields == 5 ? at(4) : nullptr, at(2), at(3)};
   }
+  template <typename T> const T* shift() const { return static_cast<const T*>(shift_base()); }
   template <typename T> HaloBufs<T> halo() const;
   template <typename T> void init_impl(hipStream_t s);
   template <typename T> void kernel_a(hipStream_t s, int part = 0);  // k_pcg_a, or the pcg1 sweep

@@ -84,7 +84,8 @@ enum AblBits : int {
 
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
-                 double* partials, const TileCfg& tc, hipStream_t s, double sigma = 0.0);
+                 double* partials, const TileCfg& tc, hipStream_t s, double sigma = 0.0,
+                 const T* shift = nullptr);  // shift: as InitData::shift
 
 // k_init with data (GpuSubdomainSolver::set_init_data / residual_norm), on launch_init's tiling.
 //   data init (measure = false): r holds f on the owned nodes (has_f; else the constant G.F), w holds
@@ -108,6 +109,9 @@ struct InitData {
   int rho_b = 0;
   // screened problem (ProblemSpec::sigma): != 0 launches the kernels built for A + sigma I, D + sigma
   double sigma = 0.0;
+  // a session with a reaction field: its shift field T(sigma + c) at local (0, 0), the fields' layout; non-null
+  // launches the kernels that read the node's own shift instead of sigma
+  const T* shift = nullptr;
 };
 template <typename T>
 void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
@@ -151,7 +155,8 @@ size_t pcg1_order_slots(const TileCfg& tc);  // d_order capacity pcg1_build_orde
 template <typename T>
 void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0, T* p1,
                  double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part = 0,
-                 bool wsweep = false, double sigma = 0.0);  // sigma: ProblemSpec::sigma (!= 0: the SH sweeps)
+                 bool wsweep = false, double sigma = 0.0,  // sigma: ProblemSpec::sigma (!= 0: the SH sweeps)
+                 const T* shift = nullptr);  // the shift field of a reaction session (the field sweeps), else null
 
 // pcg1 sweep with block tiles (pcg1_block.hip): one workgroup per tc.rows x 124 tile, the three
 // pipeline stages row-parallel; undecomposed fp64 grids; partial sums per tile as k_pcg1.  With a ticket the sweep also finishes the reduction (red_c =
@@ -310,6 +315,12 @@ template <typename T>
 void launch_scatter(const double* src, int64_t ld, T* dst, int64_t pitch, int rows, int cols, hipStream_t s);
 // *flag <- 1 if any of the rows x cols values is not finite (the caller zeroes it first)
 void launch_finite_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s);
+// A reaction field (io_kernels.hip).  launch_scatter with dst = T(sigma + src), rounded once; and the check of
+// its values: *flag <- 1 for a NaN, an infinity or a negative value among the rows x cols values
+template <typename T>
+void launch_scatter_shift(const double* src, int64_t ld, T* dst, int64_t pitch, int rows, int cols, double sigma,
+                          hipStream_t s);
+void launch_reaction_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s);
 // local nodes (li0 .. li0+rows-1) x (lj0 .. lj0+cols-1) of a subdomain with local (0, 0) at global
 // (gi0, gj0) -> out[gi * ld + gj]: w + ca pa (+ cb pb) as launch_error_norms forms it (w, pa, pb point to
 // local (0, 0), row stride pitch); nodes on the global boundary (gi in {0, M}, gj in {0, N}) get zero
@@ -327,6 +338,12 @@ void launch_gather(const T* w, const T* pa, double ca, const T* pb, double cb, i
 struct ApplyCoef {
   double alpha = 1.0, beta = 0.0, gamma = 0.0, c0 = 0.0, sigma = 0.0;
   int plain = 1;
+  // a session with a reaction field: the shift field T(sigma + c) of the subdomain that owns the block, at its
+  // local (0, 0) -- global (sgi0, sgj0) -- with row pitch spitch and selem bytes per element; read in
+  // sigma's place.  Null: sigma.
+  const void* shift = nullptr;
+  int64_t spitch = 0;
+  int sgi0 = 0, sgj0 = 0, selem = 8;
 };
 void launch_apply(const DevGeom& G, const DevTables& Tb, const double* x, int64_t ldx, const double* y, int64_t ldy,
                   double* out, int64_t ldo, int gi_lo, int gj_lo, int rows, int cols, const ApplyCoef& K,

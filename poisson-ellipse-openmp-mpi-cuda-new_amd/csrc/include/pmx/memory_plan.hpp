@@ -24,12 +24,17 @@ struct MemoryPlan {
   size_t face_off = 0;     // s-step face-coefficient fields (a, b; fp64 in the fields' pitch): the element
   size_t face_bytes = 0;   // offset of local (0,0) and the bytes of one of the two (0: none)
   size_t table_bytes = 0;  // the 1D face tables and row classes (upload_tables)
+  // The shift field of a session with a reaction field: T(sigma + c) per node, one more field of field_bytes
+  // with r's pitch and ghost layers, behind the nfields iteration fields (index shift_field()).  0 without:
+  // every other plan is what it was.
+  int nshift = 0;
 
   MemoryPlan() = default;
   // algo: 1 pcg1, 2 pcg2, 3 the s-step PCG (GpuOptions::algo); ghost_rows: 2, or the s-step's s / 2s on
   // decomposed grids -- rows, and columns on 2-D blocks
-  MemoryPlan(const ProblemSpec& spec, const Subdomain& sd, DType dtype, int algo, int ghost_rows)
-      : elem(dtype == DType::kFp64 ? 8 : 4), align(256 / elem), gh(ghost_rows), nfields(algo == 1 || algo == 3 ? 5 : 4) {
+  MemoryPlan(const ProblemSpec& spec, const Subdomain& sd, DType dtype, int algo, int ghost_rows, bool shift = false)
+      : elem(dtype == DType::kFp64 ? 8 : 4), align(256 / elem), gh(ghost_rows), nfields(algo == 1 || algo == 3 ? 5 : 4),
+        nshift(shift ? 1 : 0) {
     const auto round_up = [](size_t x, size_t a) { return (x + a - 1) / a * a; };
     const bool ca = algo == 3;
     // +8 columns of padding: vector loads of VEC <= 4 columns starting at <= ny+3 stay in the row, and the
@@ -50,7 +55,8 @@ struct MemoryPlan {
                   8 * size_t(spec.M + 2) * sizeof(int);
   }
 
-  size_t fields_total() const { return size_t(nfields) * field_bytes; }
+  size_t fields_total() const { return size_t(nfields + nshift) * field_bytes; }
+  int shift_field() const { return nshift ? nfields : -1; }  // at()'s index of the shift field, -1: none
   size_t faces_total() const { return 2 * face_bytes; }
   size_t total() const { return fields_total() + faces_total() + table_bytes; }
   size_t row_bytes() const { return size_t(pitch) * elem; }

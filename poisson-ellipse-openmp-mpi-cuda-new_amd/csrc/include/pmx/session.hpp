@@ -37,6 +37,15 @@ struct SessionConfig {
   // rehearsals) passes its world size, so every rank sizes the iteration algorithm's fields against
   // the device it shares (choose_algo; the torch path's comm_layout(sharing=...) likewise).
   int sharing = 0;
+  // Reaction field c(x, y) >= 0: the session solves (A + (sigma + c) I) u = f.  A global (M+1) x (N+1) fp64
+  // array (UserField below: host or device memory; box-boundary values are ignored and never read), consumed
+  // by the constructor.  Runs under the screened problem's rules (apply_sigma_rules) on sessions that own
+  // every subdomain; std::invalid_argument, before anything is allocated, otherwise and for a NaN, an
+  // infinity or a negative value on an interior node.
+  const double* reaction = nullptr;
+  int64_t reaction_ld = 0;
+  bool reaction_on_device = false;
+  hipStream_t reaction_stream = nullptr;
 };
 
 // A global (M+1) x (N+1) fp64 field handed to a session: host memory, or memory of the session's
@@ -101,6 +110,12 @@ class Session {
   // std::invalid_argument unless the session owns every subdomain (self / local communicator) on one device.
   void apply_device(const UserField& x, const UserField& out, const UserField& y, double alpha, double beta,
                     double gamma, double c0);
+  // Replace the reaction field of a session built with one (SessionConfig::reaction): checked like the
+  // constructor's before the session is touched, then every subdomain rewrites its shift field in place
+  // (GpuSubdomainSolver::set_reaction) -- same addresses, so the captured graphs stay valid.  The iteration
+  // state belongs to the old operator afterwards: step() throws until the next init() / solve().
+  void set_reaction(const UserField& c);
+  bool has_reaction() const { return cfg_.reaction != nullptr; }
   void step(int64_t n);
   void synchronize();
   RunStats solve(int poll_batches = 1);
@@ -112,7 +127,7 @@ class Session {
   void save_checkpoint(const std::string& path);
   void load_checkpoint(const std::string& path);
   std::string checkpoint_file(const std::string& path, int rank) const;
-  // checkpoints do not record ProblemSpec::sigma: std::invalid_argument when it is not 0
+  // checkpoints do not record ProblemSpec::sigma or a reaction field: std::invalid_argument with either
   void require_no_sigma(const char* what) const;
   RunStats profile(int64_t n);  // threaded: every bucket is the MAX over the owned ranks
   PcgState state(int i = 0);
@@ -164,6 +179,11 @@ class Session {
   void hand_over(hipStream_t consumer);  // `consumer` waits for every session stream's work so far
   // throws std::invalid_argument naming the first device field with a non-finite value
   void check_finite(const UserField& rhs, const UserField& w0);
+  // throws std::invalid_argument unless c is finite and >= 0 on every interior node (a device field: one
+  // k_reaction_check launch on its producer's stream)
+  void check_reaction(const UserField& c) const;
+  void upload_reaction(const UserField& c);
+  bool stale_ = false;  // set_reaction since the last init: the iteration state is the old operator's
 
   SessionConfig cfg_;
   ProcGrid pg_;

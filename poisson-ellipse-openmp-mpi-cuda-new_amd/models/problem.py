@@ -162,6 +162,18 @@ class PoissonEllipse:
             raise ValueError(f"{name} holds non-finite values")
         return np.ascontiguousarray(a)
 
+    def reaction_field(self, c, name: str = "reaction") -> Optional[np.ndarray]:
+        """A reaction field c(x, y) as a C-contiguous float64 (M+1)x(N+1) array, or None: field()'s type, dtype
+        and shape rules; finite and >= 0 on the interior nodes, the box-boundary values ignored (ValueError
+        otherwise -- the native entry points apply the same rules)."""
+        if c is None:
+            return None
+        a = self._host_array(c, name)
+        inner = a[1:-1, 1:-1]
+        if not (np.isfinite(inner).all() and (inner >= 0).all()):
+            raise ValueError(f"{name} must be finite and >= 0 on every interior node")
+        return np.ascontiguousarray(a)
+
     def _host_array(self, a, name: str, writable: bool = False) -> np.ndarray:
         """field()'s type, dtype and shape rules without its finiteness scan (apply's arguments)."""
         if hasattr(a, "numpy") and hasattr(a, "device"):  # a torch tensor
@@ -180,14 +192,18 @@ class PoissonEllipse:
         return a
 
     def apply(self, x, out=None, *, alpha: float = 1.0, beta: float = 0.0, y=None, gamma: float = 1.0,
-              const: float = 0.0) -> np.ndarray:
+              const: float = 0.0, reaction=None) -> np.ndarray:
         """alpha L x + beta x + gamma y + const on the interior nodes and 0 on the box boundary, on the host
         (the CPU oracle's stencil); L = A + sigma I with this problem's sigma, the plain matrix on the whole
         box -- fictitious region included, no ellipse mask.  The host twin of Session.apply: NumPy arrays
         (or CPU tensors) of shape (M+1, N+1) float64 in, a NumPy array out (`out` when given; it may be y
         and must not overlap x).  Boundary values of x count as 0 and are not read.  x is not scanned for
-        non-finite values: a NaN propagates to the nodes whose stencil reads it."""
+        non-finite values: a NaN propagates to the nodes whose stencil reads it.
+
+        reaction: optional field c(x, y) >= 0 (reaction_field()'s rules): L = A + (sigma + c) I, the operator of
+        a session built with that field."""
         xa = self._host_array(x, "x")
+        ca = self.reaction_field(reaction)
         ya = None if y is None else self._host_array(y, "y")
         oa = None if out is None else self._host_array(out, "out", writable=True)
         for name, v in (("alpha", alpha), ("beta", beta), ("gamma", gamma), ("const", const)):
@@ -197,7 +213,7 @@ class PoissonEllipse:
             raise ValueError("out overlaps x")
         r = _native().cpu_apply(self.to_native(), np.ascontiguousarray(xa),
                                 None if ya is None else np.ascontiguousarray(ya), float(alpha), float(beta),
-                                float(gamma), float(const))
+                                float(gamma), float(const), reaction=ca)
         if oa is None:
             return r
         oa[...] = r

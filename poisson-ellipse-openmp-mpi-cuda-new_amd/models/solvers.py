@@ -60,7 +60,12 @@ def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
     reports Result.extra["residual"] / ["residual_ref"]; diff keeps the last |alpha| ||p||.  hip runs it on pcg1
     (march and block tiles), pcg2 (exact=True included) and the s-step PCG; auto keeps its choice.  The
     reference's absolute breakdown guard (breakdown_tol = 1e-15) fires before a tight rtol is reached on data of
-    the default size: lower it (0 = off) with such tolerances."""
+    the default size: lower it (0 = off) with such tolerances.
+
+    reaction (every backend): an (M+1)x(N+1) float64 field c(x, y), finite and >= 0 on the interior nodes (its
+    box-boundary values are ignored and never read): the solve is (-Δ + σ + c) u = f, with D + σ + c as the
+    Jacobi diagonal.  hip runs it under sigma's rules (pcg1 on the row march; ValueError for algo="ca" / "pcg2",
+    exact=True, block_tiles=1) and also takes a float64 tensor on its device; see make_session."""
     if backend in ("cpu", "serial"):
         return solve_cpu(problem, threads=1, **kw)
     if backend in ("omp", "openmp"):
@@ -82,17 +87,20 @@ def _residual_extra(r) -> dict:
     return {k: r[k] for k in ("residual", "residual_ref") if k in r}
 
 
-def solve_cpu(problem: PoissonEllipse, threads: int = 1, keep_solution: bool = True, rhs=None, w0=None) -> Result:
-    r = _native().cpu_solve(problem.to_native(), int(threads), bool(keep_solution), rhs=rhs, w0=w0)
+def solve_cpu(problem: PoissonEllipse, threads: int = 1, keep_solution: bool = True, rhs=None, w0=None,
+              reaction=None) -> Result:
+    r = _native().cpu_solve(problem.to_native(), int(threads), bool(keep_solution), rhs=rhs, w0=w0,
+                            reaction=reaction)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
                   backend="cpu" if threads <= 1 else f"omp{threads}", extra=_residual_extra(r))
 
 
 def solve_cpu_decomposed(problem: PoissonEllipse, ranks: int = 4, split: str = "reference",
-                         threads: int = 1, keep_solution: bool = True, rhs=None, w0=None) -> Result:
+                         threads: int = 1, keep_solution: bool = True, rhs=None, w0=None,
+                         reaction=None) -> Result:
     n = _native()
     r = n.cpu_solve_decomposed(problem.to_native(), int(ranks), getattr(n.Split, split), int(threads),
-                               bool(keep_solution), rhs=rhs, w0=w0)
+                               bool(keep_solution), rhs=rhs, w0=w0, reaction=reaction)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
                   backend="cpu-decomposed", ranks=ranks, extra=_residual_extra(r))
 
@@ -103,7 +111,7 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
                  overlap: bool = True, vec_b: int = 0, waves_b: int = 0, tile_rows_b: int = -1,
                  poison_halos: bool = False, b_ring: bool = False, placement: int = 0,
                  placement_budget_s: float = 0.5, placement_keep_free: float = 0.5, block_tiles: int = -1,
-                 algo: str | int = -1, ca_s: int = 3):
+                 algo: str | int = -1, ca_s: int = 3, reaction=None):
     """Native GPU session with `ranks` subdomains on one device (LocalComm when ranks > 1).
 
     overlap: ghost exchange on a second stream concurrent with pcg_b (only matters for ranks > 1).
@@ -123,7 +131,17 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
     algo: -1 / "auto" (the library's choice: the s-step on grids of >= 6M points -- one GPU, row strips
     or 2-D blocks -- when its fields fit, else pcg1 / pcg2), "pcg1" / 1, "pcg2" / 2, or "ca" / 3 -- the
     s-step PCG (ca_kernels.hip: ca_s = 2 or 3 iterations per fused pass and one reduction; fp64, fp32
-    or mixed storage, fp64 basis and sums)."""
+    or mixed storage, fp64 basis and sums).
+
+    reaction: an (M+1)x(N+1) float64 field c(x, y), finite and >= 0 on the interior nodes (box-boundary values
+    ignored and never read): the session's operator is L = A + (σ + c) I -- in its solves, residual_norm and
+    apply -- with D + σ + c as the Jacobi diagonal.  A NumPy array, a CPU tensor, or a float64 tensor on the
+    session's device (unit column stride, row stride >= N+1; read in place by a kernel after the work already
+    enqueued on its stream).  The session keeps T(σ + c), rounded ONCE to its storage type T, in one more
+    field (the shift field): with dtype "fp32" / "mixed" its operator is A + fp32(σ + c) everywhere.
+    Session.set_reaction(c) replaces the field in place (captured graphs stay valid); step() then raises until
+    the next init() / solve().  The rules of sigma != 0 apply at any sigma: pcg1 on the row march, ValueError
+    for algo="ca" / "pcg2", exact=True, block_tiles=1 and checkpoints; error_norms needs exact=."""
     n = _native()
     algo = {"auto": -1, "pcg1": 1, "pcg2": 2, "ca": 3}.get(algo, algo) if isinstance(algo, str) else algo
     return n.Session(problem.to_native(), world=int(ranks), comm="self" if ranks == 1 else "local",
@@ -132,7 +150,7 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
                      check=check, overlap=overlap, vec_b=vec_b, waves_b=waves_b, tile_rows_b=tile_rows_b,
                      poison_halos=poison_halos, b_ring=b_ring, placement=placement,
                      placement_budget_s=placement_budget_s, placement_keep_free=placement_keep_free,
-                     block_tiles=block_tiles, algo=int(algo), ca_s=int(ca_s))
+                     block_tiles=block_tiles, algo=int(algo), ca_s=int(ca_s), reaction=reaction)
 
 
 def solve_hip(problem: PoissonEllipse, ranks: int = 1, keep_solution: bool = True, poll_batches: int = 1,

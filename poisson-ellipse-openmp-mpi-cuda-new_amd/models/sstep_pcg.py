@@ -80,10 +80,12 @@ def moment_gram(Y: list, D: torch.Tensor, s: int, h: float) -> torch.Tensor:
 
 
 class TorchSStepPCG:
-    def __init__(self, problem, s: int = 3, device="cpu", gram: str = "moments"):
+    def __init__(self, problem, s: int = 3, device="cpu", gram: str = "moments", reaction=None):
         self.gram = gram
         if s < 1:
             raise ValueError("s must be >= 1")
+        if reaction is not None:
+            raise ValueError("the s-step PCG is not built for a reaction field")
         if getattr(problem, "sigma", 0.0) != 0.0:
             raise ValueError("the s-step PCG is not built for sigma != 0")
         self.p = problem

@@ -19,7 +19,9 @@ from .solvers import Result
 
 
 class TorchPCG:
-    def __init__(self, problem, device="cpu", dtype=torch.float64, comm=None, split="reference"):
+    def __init__(self, problem, device="cpu", dtype=torch.float64, comm=None, split="reference", reaction=None):
+        """reaction: optional global (M+1)x(N+1) float64 field c >= 0 (NumPy or a CPU tensor; boundary values
+        ignored): the operator is A + (sigma + c) I, the diagonal D + sigma + c."""
         self.p = problem
         self.comm = comm or SingleComm()
         self.device = torch.device(device)
@@ -28,6 +30,10 @@ class TorchPCG:
         self.sd = subdomain(problem.M, problem.N, Px, Py, self.comm.rank)
         self.a, self.b, self.B = R.assemble(problem, self.sd, self.device, dtype)
         self.nbs = neighbours(self.sd)
+        self.shift = problem.sigma  # a number, or with a reaction field the (nx, ny) tensor sigma + c
+        c = problem.reaction_field(reaction)
+        if c is not None:
+            self.shift = (problem.sigma + self._local(c)[1:-1, 1:-1].to(torch.float64)).to(dtype)
 
     def _exchange(self, p: torch.Tensor):
         sends = [edge_view(p, s, ghost=False).contiguous() for s in range(4)]
@@ -73,13 +79,13 @@ class TorchPCG:
         rho_b = None
         if w0 is not None:
             if residual_rule:  # rho_B = (D^-1 B, B) while r still holds B
-                zb = R.precond(self.r, self.a, self.b, h1, h2, P.sigma)
+                zb = R.precond(self.r, self.a, self.b, h1, h2, self.shift)
                 rho_b = self._allsum(R.dot(zb, self.r[1:-1, 1:-1], h1, h2))
             wl = self._local(w0)  # the ring comes from the global array: no exchange
-            self.r[1:-1, 1:-1] -= R.apply_A(wl, self.a, self.b, h1, h2, P.sigma)
+            self.r[1:-1, 1:-1] -= R.apply_A(wl, self.a, self.b, h1, h2, self.shift)
             self.w[1:-1, 1:-1] = wl[1:-1, 1:-1]
         self.pv = torch.zeros_like(self.w)
-        z = R.precond(self.r, self.a, self.b, h1, h2, P.sigma)
+        z = R.precond(self.r, self.a, self.b, h1, h2, self.shift)
         self.pv[1:-1, 1:-1] = z
         self.zr_old = self._allsum(R.dot(z, self.r[1:-1, 1:-1], h1, h2))
         self.k = 1
@@ -107,7 +113,7 @@ class TorchPCG:
             k = self.k
             self.iters = k
             self._exchange(p)
-            Ap = R.apply_A(p, a, b, h1, h2, P.sigma)
+            Ap = R.apply_A(p, a, b, h1, h2, self.shift)
             denom = self._allsum(R.dot(Ap, p[1:-1, 1:-1], h1, h2))
             tol = P.breakdown_tol
             if (abs(denom) < tol) if weighted else (denom < tol):
@@ -117,7 +123,7 @@ class TorchPCG:
             w_old = w[1:-1, 1:-1].clone()
             w[1:-1, 1:-1] += alpha * p[1:-1, 1:-1]
             r[1:-1, 1:-1] -= alpha * Ap
-            z = R.precond(r, a, b, h1, h2, P.sigma)
+            z = R.precond(r, a, b, h1, h2, self.shift)
             zr_new = self._allsum(R.dot(z, r[1:-1, 1:-1], h1, h2))
             dw = w[1:-1, 1:-1] - w_old
             dsum = self._allsum((dw * dw).sum(dtype=torch.float64))

@@ -12,7 +12,10 @@ from ..utils.native import load as _native
 
 
 class DeviceOps:
-    def __init__(self, problem, Px: int = 1, Py: int = 1, rank: int = 0, device: int = 0):
+    def __init__(self, problem, Px: int = 1, Py: int = 1, rank: int = 0, device: int = 0, reaction=None):
+        if reaction is not None:
+            raise ValueError("DeviceOps evaluates -div(k grad u) alone: not built for a reaction field (use a native "
+                             "session: solve(problem, 'hip', reaction=c) / make_session(problem, reaction=c))")
         if getattr(problem, "sigma", 0.0) != 0.0:
             raise ValueError("DeviceOps evaluates -div(k grad u) alone: not built for sigma != 0 (use a native "
                              "session: solve(problem, 'hip') / make_session)")

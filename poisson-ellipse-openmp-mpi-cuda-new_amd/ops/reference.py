@@ -76,18 +76,24 @@ def assemble(problem, sd, device="cpu", dtype=torch.float64):
     return a.to(dtype), b.to(dtype), B.to(dtype)
 
 
+def _shifted(sigma) -> bool:
+    """sigma: a number, or an (nx, ny) tensor (or array, with array arguments) -- the per-node shift sigma + c of
+    a reaction field."""
+    return not isinstance(sigma, (int, float)) or sigma != 0.0
+
+
 def apply_A(p, a, b, h1, h2, sigma=0.0):
-    """(A p) on the interior, plus sigma p for the screened problem; p must carry valid ghosts.
-    Returns (nx, ny)."""
+    """(A p) on the interior, plus sigma p for the screened problem (sigma: a number or an (nx, ny) tensor of
+    per-node shifts); p must carry valid ghosts.  Returns (nx, ny)."""
     c = p[1:-1, 1:-1]
     ax = -1.0 / h1 * (a[2:, 1:-1] * (p[2:, 1:-1] - c) / h1 - a[1:-1, 1:-1] * (c - p[:-2, 1:-1]) / h1)
     ay = -1.0 / h2 * (b[1:-1, 2:] * (p[1:-1, 2:] - c) / h2 - b[1:-1, 1:-1] * (c - p[1:-1, :-2]) / h2)
-    return (ax + ay) + sigma * c if sigma != 0.0 else ax + ay
+    return (ax + ay) + sigma * c if _shifted(sigma) else ax + ay
 
 
 def diag(a, b, h1, h2, sigma=0.0):
     D = (a[2:, 1:-1] + a[1:-1, 1:-1]) / (h1 * h1) + (b[1:-1, 2:] + b[1:-1, 1:-1]) / (h2 * h2)
-    return D + sigma if sigma != 0.0 else D
+    return D + sigma if _shifted(sigma) else D
 
 
 def precond(r, a, b, h1, h2, sigma=0.0):
