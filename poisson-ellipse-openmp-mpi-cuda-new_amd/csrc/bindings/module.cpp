@@ -40,8 +40,9 @@ struct FieldArg {
   const double* ptr = nullptr;
 };
 // reaction: a reaction field instead -- the same type, dtype and shape rules; finite and >= 0 on the interior
-// nodes, its box-boundary values ignored and not read.
-FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::string& name, bool reaction = false) {
+// nodes, its box-boundary values ignored and not read.  kind 2: a diffusion field -- finite and > 0 on EVERY node.
+FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::string& name, int kind = 0) {
+  const bool reaction = kind == 1;
   FieldArg f;
   if (obj.is_none()) return f;
   py::object a = obj;
@@ -67,6 +68,9 @@ FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::strin
         if (!(std::isfinite(v) && v >= 0.0))
           throw py::value_error(name + " must be finite and >= 0 on every interior node");
       }
+  } else if (kind == 2) {
+    for (py::ssize_t k = 0; k < f.arr.size(); ++k)
+      if (!(std::isfinite(d[k]) && d[k] > 0.0)) throw py::value_error(name + " must be finite and > 0 on every node");
   } else {
     for (py::ssize_t k = 0; k < f.arr.size(); ++k)
       if (!std::isfinite(d[k])) throw py::value_error(name + " holds non-finite values");
@@ -135,12 +139,12 @@ struct SessionField {
   UserField f;
 };
 SessionField session_field(const py::object& obj, const ProblemSpec& sp, int device, const std::string& name,
-                           bool reaction = false) {
+                           int kind = 0) {
   SessionField r;
   if (!obj.is_none() && py::hasattr(obj, "__cuda_array_interface__")) {
     r.f = device_field(obj, sp, device, name);
   } else {
-    r.host = field_arg(obj, sp, name, reaction);
+    r.host = field_arg(obj, sp, name, kind);
     r.f = UserField(r.host.ptr);
   }
   return r;
@@ -426,46 +430,49 @@ PYBIND11_MODULE(_pmx, m) {
   // ---- CPU oracle ----
   // rhs / w0: optional (M+1) x (N+1) float64 arrays, see pmx/cpu_pcg.hpp
   // reaction: optional (M+1) x (N+1) float64 field c >= 0 (interior nodes; the boundary is not read)
+  // diffusion: optional (M+1) x (N+1) float64 field k > 0 on every node (the box boundary included)
   m.def("cpu_solve", [](const ProblemSpec& s, int threads, bool keep, py::object rhs, py::object w0,
-                        py::object reaction) {
+                        py::object reaction, py::object diffusion) {
           s.validate();
           const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
-          const FieldArg c = field_arg(reaction, s, "reaction", true);
+          const FieldArg c = field_arg(reaction, s, "reaction", 1), kf = field_arg(diffusion, s, "diffusion", 2);
           SolveResult r;
-          { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep, f.ptr, w.ptr, c.ptr); }
+          { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep, f.ptr, w.ptr, c.ptr, kf.ptr); }
           return result_dict(r, s, keep);
         }, py::arg("spec"), py::arg("threads") = 1, py::arg("keep_solution") = true,
-        py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("reaction") = py::none());
+        py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("reaction") = py::none(),
+        py::arg("diffusion") = py::none());
   m.def("cpu_solve_decomposed", [](const ProblemSpec& s, int nranks, Split split, int threads, bool keep,
-                                   py::object rhs, py::object w0, py::object reaction) {
+                                   py::object rhs, py::object w0, py::object reaction, py::object diffusion) {
           s.validate();
           const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
-          const FieldArg c = field_arg(reaction, s, "reaction", true);
+          const FieldArg c = field_arg(reaction, s, "reaction", 1), kf = field_arg(diffusion, s, "diffusion", 2);
           SolveResult r;
           {
             py::gil_scoped_release nogil;
-            r = cpu_solve_decomposed(s, nranks, split, threads, keep, f.ptr, w.ptr, c.ptr);
+            r = cpu_solve_decomposed(s, nranks, split, threads, keep, f.ptr, w.ptr, c.ptr, kf.ptr);
           }
           return result_dict(r, s, keep);
         }, py::arg("spec"), py::arg("nranks"), py::arg("split") = Split::kReference,
         py::arg("threads") = 1, py::arg("keep_solution") = true, py::arg("rhs") = py::none(),
-        py::arg("w0") = py::none(), py::arg("reaction") = py::none());
+        py::arg("w0") = py::none(), py::arg("reaction") = py::none(), py::arg("diffusion") = py::none());
   // x, y: C-contiguous (M+1) x (N+1) float64 arrays, validated by the caller (PoissonEllipse.apply); no
   // finiteness scan -- a NaN of x propagates to the nodes whose stencil reads it
   m.def("cpu_apply", [](const ProblemSpec& s, py::array_t<double, py::array::c_style> x, py::object y, double alpha,
-                        double beta, double gamma, double c0, py::object reaction) {
+                        double beta, double gamma, double c0, py::object reaction, py::object diffusion) {
           s.validate();
-          const FieldArg c = field_arg(reaction, s, "reaction", true);
+          const FieldArg c = field_arg(reaction, s, "reaction", 1), kf = field_arg(diffusion, s, "diffusion", 2);
           auto fits = [&](const py::array& a) { return a.ndim() == 2 && a.shape(0) == s.M + 1 && a.shape(1) == s.N + 1; };
           py::array_t<double, py::array::c_style> ya;
           if (!y.is_none()) ya = y.cast<py::array_t<double, py::array::c_style>>();
           if (!fits(x) || (!y.is_none() && !fits(ya))) throw py::value_error("x and y must have shape (M+1, N+1)");
           const double *xp = x.data(), *yp = y.is_none() ? nullptr : ya.data();
           std::vector<double> r;
-          { py::gil_scoped_release nogil; r = cpu_apply(s, xp, yp, alpha, beta, gamma, c0, c.ptr); }
+          { py::gil_scoped_release nogil; r = cpu_apply(s, xp, yp, alpha, beta, gamma, c0, c.ptr, kf.ptr); }
           return to_numpy(r, {s.M + 1, s.N + 1});
         }, py::arg("spec"), py::arg("x"), py::arg("y") = py::none(), py::arg("alpha") = 1.0, py::arg("beta") = 0.0,
-        py::arg("gamma") = 1.0, py::arg("const") = 0.0, py::arg("reaction") = py::none());
+        py::arg("gamma") = 1.0, py::arg("const") = 0.0, py::arg("reaction") = py::none(),
+        py::arg("diffusion") = py::none());
   m.def("cpu_assemble", [](const ProblemSpec& s) {
     std::vector<double> a, b, B;
     cpu_assemble(s, a, b, B);
@@ -581,20 +588,26 @@ PYBIND11_MODULE(_pmx, m) {
 
   // The MemoryPlan of one subdomain of a pcg1 session (tests of the layout): sizes, and the byte offsets of
   // local (0, 0) of every field from the start of the fields; reaction: with the shift field
+  // diffusion: with the shift field and the two face-coefficient fields (diff_field: at()'s indices of ak, bk;
+  // diff_extra: the bytes of ak's extra row behind the last field)
   m.def("memory_plan", [](const ProblemSpec& s, int world, Split split, int rank, const std::string& dtype,
-                          bool reaction) {
+                          bool reaction, bool diffusion) {
     const Subdomain sd = decompose_2d(s.M, s.N, make_process_grid(world, s.M, s.N, split), rank);
-    const MemoryPlan p(s, sd, dtype == "fp64" ? DType::kFp64 : DType::kFp32, 1, 2, reaction);
+    const MemoryPlan p(s, sd, dtype == "fp64" ? DType::kFp64 : DType::kFp32, 1, 2, reaction, diffusion);
     py::dict d;
     d["elem"] = p.elem; d["pitch"] = p.pitch; d["gh"] = p.gh; d["nx"] = sd.nx; d["ny"] = sd.ny;
     d["field_bytes"] = p.field_bytes; d["nfields"] = p.nfields; d["shift_field"] = p.shift_field();
     d["fields_total"] = p.fields_total(); d["total"] = p.total();
     py::list at;
-    for (int f = 0; f < p.nfields + p.nshift; ++f) at.append(p.at(f));
+    for (int f = 0; f < p.nfields + p.nshift + p.ndiff; ++f) at.append(p.at(f));
     d["at"] = at;
+    if (diffusion) {
+      d["ndiff"] = p.ndiff; d["diff_extra"] = p.diff_extra;
+      d["diff_field"] = py::make_tuple(p.diff_field(0), p.diff_field(1));
+    }
     return d;
   }, py::arg("spec"), py::arg("world") = 1, py::arg("split") = Split::kReference, py::arg("rank") = 0,
-     py::arg("dtype") = "fp64", py::arg("reaction") = false);
+     py::arg("dtype") = "fp64", py::arg("reaction") = false, py::arg("diffusion") = false);
 
   py::class_<OpContext>(m, "OpContext", py::module_local())
       .def(py::init<const ProblemSpec&, int, int, int, int64_t, int>(), py::arg("spec"),
@@ -677,7 +690,7 @@ PYBIND11_MODULE(_pmx, m) {
                        bool rccl_graph, bool overlap, int vec_b, int waves_b, int tile_rows_b,
                        bool poison_halos, bool b_ring, int algo, bool defer_connect, int threaded,
                        int placement, double placement_budget_s, double placement_keep_free, int sharing,
-                       int block_tiles, int ca_s, int split_sweep, py::object reaction) {
+                       int block_tiles, int ca_s, int split_sweep, py::object reaction, py::object diffusion) {
              SessionConfig c;
              s.validate();
              // type, dtype, shape, stride and device of the field (and a host field's values) before anything
@@ -687,6 +700,11 @@ PYBIND11_MODULE(_pmx, m) {
              c.reaction_ld = rf.f.ld;
              c.reaction_on_device = rf.f.on_device;
              c.reaction_stream = rf.f.stream;
+             const SessionField df = session_field(diffusion, s, devices.empty() ? device : devices[0], "diffusion", 2);
+             c.diffusion = df.f.ptr;
+             c.diffusion_ld = df.f.ld;
+             c.diffusion_on_device = df.f.on_device;
+             c.diffusion_stream = df.f.stream;
              c.sharing = sharing;
              c.spec = s;
              c.opt = make_options(device, kernel, block, vec, waves, tile_rows, dtype, exact,
@@ -722,7 +740,19 @@ PYBIND11_MODULE(_pmx, m) {
            py::arg("b_ring") = false, py::arg("algo") = -1, py::arg("defer_connect") = false,
            py::arg("threaded") = -1, py::arg("placement") = 0, py::arg("placement_budget_s") = 0.5,
            py::arg("placement_keep_free") = 0.5, py::arg("sharing") = 0, py::arg("block_tiles") = -1,
-           py::arg("ca_s") = 3, py::arg("split_sweep") = -1, py::arg("reaction") = py::none())
+           py::arg("ca_s") = 3, py::arg("split_sweep") = -1, py::arg("reaction") = py::none(),
+           py::arg("diffusion") = py::none())
+      .def("set_diffusion", [](Session& s, py::object diffusion) {
+             if (diffusion.is_none()) throw py::value_error("diffusion must be an (M+1) x (N+1) float64 field");
+             const SessionField df = session_field(diffusion, s.solver(0).spec(), s.solver(0).device(), "diffusion", 2);
+             py::gil_scoped_release g;
+             s.set_diffusion(df.f);
+           }, py::arg("diffusion"),
+           "replace the diffusion field k of a session built with one (make_session(p, diffusion=k)): the same "
+           "types and checks as there (a NumPy array, a CPU tensor or a float64 device array; finite and > 0 on "
+           "EVERY node, ValueError before the session is touched).  The face-coefficient fields are rewritten in "
+           "place, so captured graphs stay valid; step() raises until the next init() / solve()")
+      .def_property_readonly("has_diffusion", &Session::has_diffusion)
       .def("set_reaction", [](Session& s, py::object reaction) {
              if (reaction.is_none()) throw py::value_error("reaction must be an (M+1) x (N+1) float64 field");
              const SessionField rf = session_field(reaction, s.solver(0).spec(), s.solver(0).device(), "reaction", true);

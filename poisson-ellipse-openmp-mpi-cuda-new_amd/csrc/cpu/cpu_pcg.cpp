@@ -36,6 +36,23 @@ inline bool breakdown(double denom, const ProblemSpec& s) {
   return s.norm == Norm::kWeighted ? std::fabs(denom) < s.breakdown_tol : denom < s.breakdown_tol;
 }
 
+// Diffusion field k(x, y): the face coefficients become a[i,j] <- (0.5 (k[i-1,j] + k[i,j])) a[i,j] and
+// b[i,j] <- (0.5 (k[i,j-1] + k[i,j])) b[i,j] on every face between two nodes of the box (rows 1 .. M of a,
+// columns 1 .. N of b: the faces the interior stencils read); k = 1 multiplies by exactly 1.0.  a, b: local
+// arrays of pitch P whose (0, 0) is global (gi0, gj0), rows 0 .. rows-1, columns 0 .. cols-1.
+void scale_faces(std::vector<double>& a, std::vector<double>& b, int P, int gi0, int gj0, int rows, int cols,
+                 const ProblemSpec& spec, const double* k) {
+  const int M = spec.M, N = spec.N, Q = N + 1;
+  for (int li = 0; li < rows; ++li)
+    for (int lj = 0; lj < cols; ++lj) {
+      const int gi = gi0 + li, gj = gj0 + lj;
+      if (gi < 0 || gi > M || gj < 0 || gj > N) continue;
+      const size_t c = size_t(li) * P + lj, g = size_t(gi) * Q + gj;
+      if (gi >= 1) a[c] = (0.5 * (k[g - Q] + k[g])) * a[c];
+      if (gj >= 1) b[c] = (0.5 * (k[g - 1] + k[g])) * b[c];
+    }
+}
+
 }  // namespace
 
 void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<double>& b,
@@ -57,7 +74,7 @@ void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<d
 }
 
 SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, const double* rhs,
-                      const double* w0, const double* reaction) {
+                      const double* w0, const double* reaction, const double* diffusion) {
   spec.validate();
   const GridInfo g(spec);
   const geo::FaceTables t(spec, g);
@@ -86,6 +103,7 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
       a[size_t(i) * P + j] = geo::coef_a(t, g, i, j);
       b[size_t(i) * P + j] = geo::coef_b(t, g, i, j);
     }
+  if (diffusion) scale_faces(a, b, P, 0, 0, M + 2, N + 2, spec, diffusion);
   for (int i = 1; i <= M - 1; ++i)
     for (int j = 1; j <= N - 1; ++j) {
       const size_t g = size_t(i) * (N + 1) + j;
@@ -194,7 +212,7 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
 }
 
 std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const double* y, double alpha, double beta,
-                              double gamma, double c0, const double* reaction) {
+                              double gamma, double c0, const double* reaction, const double* diffusion) {
   spec.validate();
   const GridInfo g(spec);
   const geo::FaceTables t(spec, g);
@@ -208,6 +226,7 @@ std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const do
       a[size_t(i) * P + j] = geo::coef_a(t, g, i, j);
       b[size_t(i) * P + j] = geo::coef_b(t, g, i, j);
     }
+  if (diffusion) scale_faces(a, b, P, 0, 0, M + 2, N + 2, spec, diffusion);
   for (int i = 1; i <= M - 1; ++i)
     for (int j = 1; j <= N - 1; ++j) p[size_t(i) * P + j] = x[size_t(i) * Q + j];
   const bool plain = alpha == 1.0 && beta == 0.0 && !y && c0 == 0.0;
@@ -235,7 +254,7 @@ std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const do
 // ---------------------------------------------------------------------------
 
 CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads, const double* rhs,
-                           const double* w0, const double* reaction)
+                           const double* w0, const double* reaction, const double* diffusion)
     : spec_(spec), g_(spec), sd_(sd), threads_(threads < 1 ? 1 : threads) {
   const geo::FaceTables t(spec, g_);
   const int nx = sd.nx, ny = sd.ny, P = ny + 2;
@@ -250,6 +269,7 @@ CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int thr
       a_[size_t(li) * P + lj] = geo::coef_a(t, g_, gi, gj);
       b_[size_t(li) * P + lj] = geo::coef_b(t, g_, gi, gj);
     }
+  if (diffusion) scale_faces(a_, b_, P, sd.gi0(), sd.gj0(), nx + 2, ny + 2, spec, diffusion);
   for (int li = 1; li <= nx; ++li)
     for (int lj = 1; lj <= ny; ++lj) {
       const int gi = sd.gi0() + li, gj = sd.gj0() + lj;
@@ -465,13 +485,13 @@ SolveResult cpu_pcg_loop(const ProblemSpec& spec, std::vector<CpuSubdomain*>& lo
 
 SolveResult cpu_solve_decomposed(const ProblemSpec& spec, int nranks, Split split,
                                  int threads_per_rank, bool keep_solution, const double* rhs,
-                                 const double* w0, const double* reaction) {
+                                 const double* w0, const double* reaction, const double* diffusion) {
   spec.validate();
   const ProcGrid pg = make_process_grid(nranks, spec.M, spec.N, split);
   std::vector<CpuSubdomain> subs;
   subs.reserve(nranks);
   for (int r = 0; r < nranks; ++r)
-    subs.emplace_back(spec, decompose_2d(spec.M, spec.N, pg, r), threads_per_rank, rhs, w0, reaction);
+    subs.emplace_back(spec, decompose_2d(spec.M, spec.N, pg, r), threads_per_rank, rhs, w0, reaction, diffusion);
   std::vector<CpuSubdomain*> local;
   for (auto& s : subs) local.push_back(&s);
 

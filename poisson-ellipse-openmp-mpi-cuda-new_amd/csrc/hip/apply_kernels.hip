@@ -26,6 +26,10 @@
 // the subdomain that owns the launch's block (ApplyCoef::shift, its pitch and local origin) with the step's
 // other loads, and enters in sigma's place -- so apply, the solver and residual_norm share one operator,
 // for fp32 storage too.  SH = 0 / 1 are the kernels they were.
+//
+// SH = 3 (a session with a diffusion field): as 2, and the faces of a node come from the owning subdomain's
+// face-coefficient fields (ApplyCoef::ka / kb, the shift field's layout) with the step's other loads: ak of
+// the next row (carried over like the table value), bk of the node and of the column after it.
 #include <cmath>
 #include <cstdint>
 
@@ -82,6 +86,13 @@ k_apply(DevGeom G, DevTables Tb, const double* __restrict__ x, int64_t ldx, cons
   const int gi_last = gi_lo + rows - 1;
   const ColConst cc = load_col(Tb, gjc);
 
+  // SH 3: the lane's column of the face fields -- a column of the block and of the interior, so every lane
+  // reads cells the setup kernel wrote; rows clamp to the block's (local 0 .. nx+1, +1 for the next row's ak)
+  [[maybe_unused]] const int gjk = clampi(gjs, 1, N - 1);
+  [[maybe_unused]] const T* fka = static_cast<const T*>(K.ka);
+  [[maybe_unused]] const T* fkb = static_cast<const T*>(K.kb);
+  [[maybe_unused]] auto kat = [&](int gi) { return int64_t(gi - K.sgi0) * K.spitch + (gjk - K.sgj0); };
+
   auto rowin = [&](int gi) { return gi > 0 && gi < M; };
   auto xptr = [&](int gi, int j) { return x + int64_t(clampi(gi, 1, M - 1)) * ldx + j; };
 
@@ -96,7 +107,9 @@ k_apply(DevGeom G, DevTables Tb, const double* __restrict__ x, int64_t ldx, cons
     ec = ein && rowin(gi0) ? ve : 0.0;
   }
   // the row tables cover gi = 0 .. M + 1: every row of the block, and the one after it, has an entry
-  double a0 = face_a(cc, load_row(Tb, gi0).rv0, G);
+  double a0;
+  if constexpr (SH == 3) a0 = double(fka[kat(min(gi0, gi_last))]);
+  else a0 = face_a(cc, load_row(Tb, gi0).rv0, G);
 
   for (int rb = r0; rb < rend; rb += kApplyUnroll) {
     double xp[kApplyUnroll], ep[kApplyUnroll], yv[kApplyUnroll];
@@ -108,7 +121,17 @@ k_apply(DevGeom G, DevTables Tb, const double* __restrict__ x, int64_t ldx, cons
 #pragma unroll
       for (int u = 0; u < kApplyUnroll; ++u) yv[u] = y[int64_t(min(gi_lo + rb + u, gi_last)) * ldy + gjs];
     }
-    if constexpr (SH == 2) {  // local (gi - sgi0, gj - sgj0) of the owning subdomain: its nodes and boundary lines
+    [[maybe_unused]] T av[kApplyUnroll], bv0[kApplyUnroll], bv1[kApplyUnroll];
+    if constexpr (SH == 3) {
+#pragma unroll
+      for (int u = 0; u < kApplyUnroll; ++u) {
+        const int64_t o = kat(min(gi_lo + rb + u, gi_last));
+        av[u] = fka[o + K.spitch];
+        bv0[u] = fkb[o];
+        bv1[u] = fkb[o + 1];
+      }
+    }
+    if constexpr (SH >= 2) {  // local (gi - sgi0, gj - sgj0) of the owning subdomain: its nodes and boundary lines
       const T* sh = static_cast<const T*>(K.shift);
 #pragma unroll
       for (int u = 0; u < kApplyUnroll; ++u)
@@ -127,11 +150,16 @@ k_apply(DevGeom G, DevTables Tb, const double* __restrict__ x, int64_t ldx, cons
       const double xn = jin && rowin(gi + 1) ? xp[u] : 0.0;
       const double en = ein && rowin(gi + 1) ? ep[u] : 0.0;
       const double xjm = dpp_shift<kWaveShr1>(xc, ec), xjp = dpp_shift<kWaveShl1>(xc, ec);
-      const RowConst rc = load_row(Tb, gi);
-      const double a1 = face_a(cc, rc.rv1, G);
-      const double b0 = face_b(rc, cc.rh0, G), b1 = face_b(rc, cc.rh1, G);
+      double a1, b0, b1;
+      if constexpr (SH == 3) {
+        a1 = double(av[u]); b0 = double(bv0[u]); b1 = double(bv1[u]);
+      } else {
+        const RowConst rc = load_row(Tb, gi);
+        a1 = face_a(cc, rc.rv1, G);
+        b0 = face_b(rc, cc.rh0, G); b1 = face_b(rc, cc.rh1, G);
+      }
       double Lx = apply_a<true>(xc, xm, xn, xjm, xjp, a0, a1, b0, b1, G);
-      if constexpr (SH == 2) Lx = __builtin_fma(double(sv[u]), xc, Lx);
+      if constexpr (SH >= 2) Lx = __builtin_fma(double(sv[u]), xc, Lx);
       else if constexpr (SH == 1) Lx = __builtin_fma(K.sigma, xc, Lx);  // as apply_a_sh
       const double v = jin && rowin(gi) ? combine<HAS_Y>(K, Lx, xc, HAS_Y ? yv[u] : 0.0) : 0.0;
       if (owned) out[int64_t(gi) * ldo + gjs] = v;
@@ -156,7 +184,15 @@ void launch_apply(const DevGeom& G, const DevTables& Tb, const double* x, int64_
   const bool sh = K.sigma != 0.0;
 #define PMX_APPLY(...) \
   hipLaunchKernelGGL((k_apply<__VA_ARGS__>), grid, block, 0, s, G, Tb, x, ldx, y, ldy, out, ldo, gi_lo, gj_lo, rows, cols, K)
-  if (K.shift) {
+  if (K.ka) {
+    PMX_CHECK(K.shift && K.kb && (K.selem == 8 || K.selem == 4), "k_apply: a diffusion session holds the shift field "
+                                                                  "and both face fields, fp64 or fp32");
+    if (K.selem == 8 && y) PMX_APPLY(3, true, double);
+    else if (K.selem == 8) PMX_APPLY(3, false, double);
+    else if (y) PMX_APPLY(3, true, float);
+    else PMX_APPLY(3, false, float);
+  }
+  else if (K.shift) {
     PMX_CHECK(K.selem == 8 || K.selem == 4, "k_apply: the shift field is fp64 or fp32");
     if (K.selem == 8 && y) PMX_APPLY(2, true, double);
     else if (K.selem == 8) PMX_APPLY(2, false, double);

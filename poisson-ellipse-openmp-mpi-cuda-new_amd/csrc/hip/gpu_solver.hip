@@ -216,7 +216,9 @@ void apply_sigma_rules(const ProblemSpec& spec, const ProcGrid& grid, GpuOptions
   PMX_CHECK(o.resolved, "apply_sigma_rules needs resolve_options()");
   if (spec.sigma == 0.0 && !o.reaction) return;
   auto refuse = [&](const char* option) {
-    throw std::invalid_argument(std::string(o.reaction ? "a reaction field" : "sigma != 0 (the screened problem)") +
+    throw std::invalid_argument(std::string(o.diffusion  ? "a diffusion field"
+                                            : o.reaction ? "a reaction field"
+                                                         : "sigma != 0 (the screened problem)") +
                                 " runs pcg1 on the row march only: " + option + " is not built for it");
   };
   if (o.algo == 3) refuse("algo=\"ca\" (the s-step PCG)");
@@ -337,12 +339,14 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
   const int gh = ca_ && sd.grid.size() > 1 ? (ca_fuse_ ? 2 * opt_.ca_s : opt_.ca_s) : 2;
   PMX_CHECK(!pcg1_ || (!opt.exact && (sd.grid.size() == 1 || (sd.nx >= 2 && sd.ny >= 2))),
             "pcg1 needs the fast arithmetic and a subdomain of at least 2 x 2 nodes");
-  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh, opt_.reaction != 0);
+  PMX_CHECK(!opt_.diffusion || (pcg1_ && opt_.reaction), "a diffusion field runs pcg1 with the shift field");
+  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh, opt_.reaction != 0, opt_.diffusion != 0);
   const int elem = int(plan_.elem);
   geom_ = make_dev_geom(spec, sd, plan_.pitch);
   const DevGeom& G = geom_;
   {  // fail with a sizing message instead of a bare hipErrorOutOfMemory
-    const size_t need = estimate_device_bytes_algo(spec, sd, opt.dtype, opt_.algo) + plan_.nshift * plan_.field_bytes;
+    const size_t need = estimate_device_bytes_algo(spec, sd, opt.dtype, opt_.algo) +
+                        (plan_.nshift + plan_.ndiff) * plan_.field_bytes + plan_.diff_extra;
     PMX_CHECK(need <= free_b,
               "subdomain " << sd.nx << "x" << sd.ny << " (" << (ca_ ? "s-step, 7" : pcg1_ ? "pcg1, 5" : "pcg2, 4")
                            << " fields) needs " << need / 1e9 << " GB on device " << opt.device
@@ -430,7 +434,8 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
       wtrace_ = pcg1_wave_trace_setup(std::atoll(e), wtrace_n_);
     }
 #endif
-    tiles1_.arith32 = elem == 4 && opt_.arith32 ? 1 : 0;
+    // (a diffusion session runs fp64 registers on fp32 storage too: no packed-fp32 diffusion sweep is built)
+    tiles1_.arith32 = elem == 4 && opt_.arith32 && !opt_.diffusion ? 1 : 0;
     const int waves_w = opt_.waves1w ? opt_.waves1w : (opt_.waves1 == 8 ? 4 : opt_.waves1);
     tiles1w_ = make_pcg1_tiles(G, opt_.vec1, waves_w, opt_.rows1w ? opt_.rows1w : tiles1_.rows,
                                opt_.pf1w ? opt_.pf1w : tiles1_.pf, elem);
@@ -715,6 +720,18 @@ void GpuSubdomainSolver::set_reaction(const double* c, int64_t ld, bool on_devic
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
+void GpuSubdomainSolver::set_diffusion(const double* k, int64_t ld, hipStream_t s) {
+  PMX_CHECK(has_diffusion(), "set_diffusion needs a solver built with a diffusion field (GpuOptions::diffusion)");
+  PMX_CHECK(k && ld >= spec_.N + 1, "set_diffusion needs an (M+1) x (N+1) device array with row stride >= N+1");
+  HIP_CHECK(hipSetDevice(opt_.device));
+  with_storage([&](auto t) {
+    using T = decltype(t);
+    launch_face_fields<T>(geom_, tables_, k, ld, reinterpret_cast<T*>(field_ptr(plan_.diff_field(0))),
+                          reinterpret_cast<T*>(field_ptr(plan_.diff_field(1))), s);
+  });
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
 void GpuSubdomainSolver::set_init_data_device(const double* f, const double* w0, int64_t ld_f, int64_t ld_w0) {
   PMX_CHECK(!f || ld_f >= sd_.ny, "row stride of the device right-hand side below the block's width");
   PMX_CHECK(!w0 || ld_w0 >= sd_.ny + 2, "row stride of the device initial guess below the block's width");
@@ -764,6 +781,8 @@ double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_
     X.npend = pw.n;
     X.sigma = spec_.sigma;
     X.shift = shift<T>();
+    X.ka = face<T>(0);
+    X.kb = face<T>(1);
     launch_init_data<T>(geom_, tables_, fields<T>().w, nullptr, HaloBufs<T>{}, part, init_tiles_, X, true, s);
   });
   HIP_CHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -908,6 +927,8 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     X.has_w = !stage_w_.empty() || dev_w_;
     X.sigma = spec_.sigma;
     X.shift = shift<T>();
+    X.ka = face<T>(0);
+    X.kb = face<T>(1);
     X.rho_b = stop_ref_data_ ? 1 : 0;
     // the same cells from either source: a staged host copy, or the caller's device block through the
     // scatter kernel (set_init_data_device)
@@ -934,7 +955,8 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     std::vector<char>().swap(stage_w_);
     dev_f_ = dev_w_ = nullptr;
   } else {
-    launch_init<T>(G, tables_, w, r, halo<T>(), partials_.get(), init_tiles_, s, spec_.sigma, shift<T>());
+    launch_init<T>(G, tables_, w, r, halo<T>(), partials_.get(), init_tiles_, s, spec_.sigma, shift<T>(), face<T>(0),
+                   face<T>(1));
     after_launch(s);
   }
   // red_b[1] = (z^0, r^0); red_b[0] = rho_B = (D^-1 B, B) when the residual rule starts from a w0, else 0
@@ -1025,7 +1047,7 @@ void GpuSubdomainSolver::kernel_a(hipStream_t s, int part) {
   }
   if (pcg1_)
     launch_pcg1<T>(geom_, tables_, F.w, F.r, F.r2, F.p0, F.p1, partials_.get(), state_, tiles1_for(w_sweep_next()), s,
-                   part, w_sweep_next(), spec_.sigma, shift<T>());
+                   part, w_sweep_next(), spec_.sigma, shift<T>(), face<T>(0), face<T>(1));
   else
     launch_pcg_a_wave<T>(geom_, tables_, F.r, F.p0, F.p1, halo<T>(), partials_.get(), state_, tiles_, opt_.exact, s);
 }

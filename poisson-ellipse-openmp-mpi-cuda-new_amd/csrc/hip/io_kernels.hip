@@ -4,6 +4,8 @@
 //   k_scatter  a block of the global array -> a field (or any pitched T buffer), rounded to the storage
 //              type as the host path's round_to_storage: copied for double, static_cast for float
 //   k_finite   raises a flag on any non-finite value of the whole array
+//   k_diffusion_check / k_face_fields   a diffusion field: the check of its values, and the two complete
+//              face-coefficient fields of a subdomain (geometry and k folded in) from the nodal values
 //   k_gather   w of one subdomain, pending steps applied as GpuSubdomainSolver::download_w applies them,
 //              -> its block of the global array; global boundary nodes are written as zero
 //
@@ -14,6 +16,7 @@
 // Stores to the fields are non-temporal like the sweeps' (the next reader is another kernel).
 #include <cstdint>
 
+#include "pcg_device.hpp"
 #include "pmx/common.hpp"
 #include "pmx/kernels.hpp"
 
@@ -96,6 +99,47 @@ k_reaction_check(const double* __restrict__ src, int64_t ld, int rows, int cols,
   if (bad) *flag = 1;  // every writer stores the same value
 }
 
+// k_finite for a diffusion field: raises the flag on a NaN, an infinity or a value <= 0
+__global__ void __launch_bounds__(kIoCols)
+k_diffusion_check(const double* __restrict__ src, int64_t ld, int rows, int cols, int* flag) {
+  const int j = blockIdx.x * kIoCols + threadIdx.x;
+  const int i0 = blockIdx.y * kIoRows;
+  if (j >= cols) return;
+  bool bad = false;
+#pragma unroll
+  for (int u = 0; u < kIoRows; ++u)
+    if (i0 + u < rows) {
+      const double v = src[int64_t(i0 + u) * ld + j];
+      bad |= !(v > 0.0) || v == __builtin_huge_val();  // !(v > 0): a NaN, a zero or a negative value
+    }
+  if (bad) *flag = 1;  // every writer stores the same value
+}
+
+// The face-coefficient fields of a diffusion session (launch_face_fields): one thread per local cell, rows
+// -1 .. nx+3 (the last one of ak alone), every column of the row (-1 .. pitch-2).  The geometric factor is the
+// exact formula the s-step's face fields use (coef_a / coef_b), the mean of k and the product in fp64 in the
+// order (0.5 (k' + k)) a, rounded once to T.  A face that does not join two nodes of the box gets 1: such
+// cells only ever meet masked values, but D of a masked node must not be 0.
+template <typename T>
+__global__ void __launch_bounds__(kIoCols)
+k_face_fields(DevGeom G, DevTables Tb, const double* __restrict__ k, int64_t ld, T* __restrict__ ak, T* __restrict__ bk) {
+  using namespace dev;
+  const int lj = -1 + int(blockIdx.x * kIoCols + threadIdx.x);
+  const int li = -1 + int(blockIdx.y);
+  if (lj > int(G.pitch) - 2 || li > G.nx + 3) return;
+  const int gi = G.gi0 + li, gj = G.gj0 + lj;
+  const bool node = gi >= 0 && gi <= G.M && gj >= 0 && gj <= G.N;
+  double a = 1.0, b = 1.0;
+  if (node) {
+    const double kc = k[int64_t(gi) * ld + gj];
+    if (gi >= 1) a = (0.5 * (k[int64_t(gi - 1) * ld + gj] + kc)) * coef_a(Tb, G, gi, gj);
+    if (gj >= 1) b = (0.5 * (k[int64_t(gi) * ld + gj - 1] + kc)) * coef_b(Tb, G, gi, gj);
+  }
+  const int64_t o = int64_t(li) * G.pitch + lj;
+  ak[o] = static_cast<T>(a);
+  if (li <= G.nx + 2) bk[o] = static_cast<T>(b);
+}
+
 // local nodes (li0 .. li0 + rows - 1) x (lj0 .. lj0 + cols - 1) of a subdomain whose local (0, 0) is
 // global (gi0, gj0); w, pa, pb point to local (0, 0)
 template <typename T>
@@ -148,6 +192,24 @@ void launch_reaction_check(const double* src, int64_t ld, int rows, int cols, in
   hipLaunchKernelGGL(k_reaction_check, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);
   HIP_CHECK(hipGetLastError());
 }
+
+void launch_diffusion_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s) {
+  hipLaunchKernelGGL(k_diffusion_check, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);
+  HIP_CHECK(hipGetLastError());
+}
+
+template <typename T>
+void launch_face_fields(const DevGeom& G, const DevTables& Tb, const double* k, int64_t ld, T* ak, T* bk, hipStream_t s) {
+  PMX_CHECK(k && ak && bk && ld >= G.N + 1, "face fields: need the nodal field (row stride >= N + 1) and both outputs");
+  PMX_CHECK(G.nx + 5 <= 65535, "face fields: too many rows for one launch: " << G.nx);
+  const dim3 grid(unsigned((G.pitch + kIoCols - 1) / kIoCols), unsigned(G.nx + 5));
+  hipLaunchKernelGGL((k_face_fields<T>), grid, dim3(kIoCols), 0, s, G, Tb, k, ld, ak, bk);
+  HIP_CHECK(hipGetLastError());
+}
+template void launch_face_fields<double>(const DevGeom&, const DevTables&, const double*, int64_t, double*, double*,
+                                         hipStream_t);
+template void launch_face_fields<float>(const DevGeom&, const DevTables&, const double*, int64_t, float*, float*,
+                                        hipStream_t);
 
 void launch_finite_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s) {
   hipLaunchKernelGGL(k_finite, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);

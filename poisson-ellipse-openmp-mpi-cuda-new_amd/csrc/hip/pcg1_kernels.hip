@@ -61,6 +61,10 @@ constexpr int kPcg1AutoPf = 1;
 #define PMX_PCG1_F32_WAVES_W 4
 #endif
 constexpr int kPcg1F32Waves = PMX_PCG1_F32_WAVES, kPcg1F32WavesW = PMX_PCG1_F32_WAVES_W;
+// waves per SIMD of the diffusion sweeps (WS: the w sweep), see pcg1_min_waves
+#ifndef PMX_PCG1_DIF_WAVES
+#define PMX_PCG1_DIF_WAVES(WS) 2
+#endif
 
 #ifdef PMX_WAVE_TRACE
 // Diagnostic build only (bench/wave_trace.sh): per-wave start/end wall clock, XCC and HW ids and
@@ -87,6 +91,9 @@ __device__ long long g_wtrace_it = -1;
 //    twins' 123 (plain) / 163 (w) at PF 1.  Held to the twins' bounds of 128 / 168 they spill (44 / 76 VGPRs,
 //    104 / 124 B of scratch), so they are bounded one class lower -- plain sweeps at 3 waves per SIMD, w sweeps
 //    at 2 -- and compile without scratch (profiles/r11/reaction/).
+//  * the diffusion sweeps (DIF, a session with a diffusion field) carry five more rows (x faces of rows m, m-1,
+//    m-2; y faces of rows m-1, m-2, three columns each) and prefetch 2 VEC + 1 more values per slot, and need
+//    none of the table constants: see pcg1_min_waves and profiles/r12/diffusion/.
 template <typename T, typename C, int VEC, int WAVES, int PF, bool WS>
 constexpr int pcg1_min_waves_base() {
   // lockstep workgroups (WAVES 4 / 8, fp64, prefetch 1): the plain sweep at 4 waves per SIMD (2
@@ -98,10 +105,11 @@ constexpr int pcg1_min_waves_base() {
   if (!WS && (PF == 1 || (sizeof(T) == 4 && PF <= 3) || (sizeof(T) == 8 && PF == 2))) return 4;
   return PF <= 2 ? 3 : 2;  // the w sweeps (triple paths) and fp64 PF 3
 }
-template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int SH = 0>
+template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int SH = 0, bool DIF = false>
 constexpr int pcg1_min_waves() {
   constexpr int base = pcg1_min_waves_base<T, C, VEC, WAVES, PF, WS>();
   if (SH != 2) return base;
+  if (DIF) return PMX_PCG1_DIF_WAVES(WS);
   // (the fp32-arithmetic w sweeps run at 4: their field twins still spill 2 VGPRs at 3 with prefetch 2)
   return std::max(1, base - (WS && std::is_same_v<C, float> ? 2 : 1));
 }
@@ -116,6 +124,10 @@ struct Pcg1Part {
   // the subdomain's shift field T(sigma + c) at local (0, 0), in the fields' storage type and layout: read
   // by the field sweeps (SH = kShiftField) only
   const void* shift;
+  // the subdomain's face-coefficient fields ak, bk at local (0, 0), as the shift field: read by the diffusion
+  // sweeps (DIF) only
+  const void* ka;
+  const void* kb;
 };
 
 // k-th tile of the part -> (ti, tj); false past the end.  The frame is enumerated as: tile rows
@@ -151,8 +163,11 @@ __host__ __device__ inline bool pcg1_tile(int k, const Pcg1Part& P, int tiles_j,
 // D + sigma, sigma from Pcg1Part.  launch_pcg1 picks it; SH = 0 is the sweep of every other solve.
 // SH = kShiftField (2): the sweep of a session with a reaction field -- the shift of every node from
 // Pcg1Part::shift, loaded with r and p (one more row per fetch, two more carried rows).
-template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int DPF = 0, int SH = kShiftNone>
-__global__ void __launch_bounds__(64 * WAVES, (pcg1_min_waves<T, C, VEC, WAVES, PF, WS, SH>()))
+// DIF: the sweep of a session with a diffusion field (on top of SH = kShiftField): the faces of every node from
+// Pcg1Part::ka / kb (pcg1_march's DIF).
+template <typename T, typename C, int VEC, int WAVES, int PF, bool WS, int DPF = 0, int SH = kShiftNone,
+          bool DIF = false>
+__global__ void __launch_bounds__(64 * WAVES, (pcg1_min_waves<T, C, VEC, WAVES, PF, WS, SH, DIF>()))
 k_pcg1(DevGeom G, DevTables Tb, T* __restrict__ w, T* r, T* r2, T* p0, T* p1,
        double* __restrict__ partials, PcgState* S, int TI, int tiles_j, int ntiles, Pcg1Part part) {
   constexpr int WO = 64 * VEC - 4;  // owned columns per tile
@@ -207,9 +222,16 @@ k_pcg1(DevGeom G, DevTables Tb, T* __restrict__ w, T* r, T* r2, T* p0, T* p1,
                   SH == kShiftSigma ? float(part.sigma) : 0.0f, SH == kShiftSigma ? part.sigma : 0.0};
   [[maybe_unused]] const T* shf = nullptr;
   if constexpr (SH == kShiftField) shf = static_cast<const T*>(part.shift);
+  [[maybe_unused]] const T* fka = nullptr;
+  [[maybe_unused]] const T* fkb = nullptr;
+  if constexpr (DIF) {
+    fka = static_cast<const T*>(part.ka);
+    fkb = static_cast<const T*>(part.kb);
+  }
 #define PMX_MARCH(E, F)                                                                                       \
-  pcg1_march<T, C, VEC, PF, E, F, 0, (WAVES > 1), SH>(G, Tb, AF, w, rold, rnew, pold, pnew, i0, i1, j0, j1, alpha, \
-                                                    beta, c1, c2, acc, scol, ocls, use_cls, nullptr, shf)
+  pcg1_march<T, C, VEC, PF, E, F, 0, (WAVES > 1), SH, DIF>(G, Tb, AF, w, rold, rnew, pold, pnew, i0, i1, j0, j1,   \
+                                                         alpha, beta, c1, c2, acc, scol, ocls, use_cls, nullptr, \
+                                                         shf, fka, fkb)
   // LDS-DMA ring of the FAST march (pcg1_march's DPF mode): DPF slots of r, p (, w) rows per wave
   constexpr int kRingDoubles = DPF > 0 ? DPF * (WS ? 3 : 2) * 128 : 2;
   __shared__ double s_ring[WAVES * kRingDoubles];
@@ -487,7 +509,7 @@ int pcg1_build_order(const DevGeom& G, const DevTables& Tb, TileCfg& tc, Pcg1Slo
   std::vector<Pcg1Slot> order(3 * per, Pcg1Slot{-1, 0, 0ull});
   int nslow = 0;
   for (int part = 0; part <= 2; ++part) {
-    const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, nullptr, 0, 0.0, nullptr};
+    const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, nullptr, 0, 0.0, nullptr, nullptr, nullptr};
     const int count = part == 0 ? n : part == 1 ? tc.interior_tiles() : n - tc.interior_tiles();
     // groups: runs of up to gw consecutive tiles of the part's enumeration within one tile row
     std::vector<std::vector<int>> groups;
@@ -596,7 +618,7 @@ int pcg1_lds_pad(int wpcu, int waves) {
 template <typename T>
 void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0, T* p1,
                  double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part, bool wsweep,
-                 double sigma, const T* shift) {
+                 double sigma, const T* shift, const T* ka, const T* kb) {
   PMX_CHECK(tc.kind == 3, "launch_pcg1 needs make_pcg1_tiles");
   PMX_CHECK(part >= 0 && part <= 2, "launch_pcg1: part must be 0, 1 or 2");
   const int tiles = part == 0 ? tc.ntiles() : part == 1 ? tc.interior_tiles() : tc.ntiles() - tc.interior_tiles();
@@ -606,7 +628,7 @@ void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0
   PMX_CHECK(tc.waves == 1 || grouped, "pcg1: workgroups of several waves need the grouped dispatch order");
   const int nb = grouped ? tc.groups[part] : tiles;
   const int count = grouped ? nb * tc.waves : tiles;
-  const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, ord, count, sigma, shift};
+  const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, ord, count, sigma, shift, ka, kb};
   if (tiles == 0) return;
   PMX_CHECK(G.nb == 0 || (G.nx >= 2 && G.ny >= 2), "pcg1 on a decomposed grid needs subdomains >= 2 x 2");
   const int bs = 64 * tc.waves;
@@ -654,6 +676,27 @@ void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0
       PMX_PCG1_SH(double, 2, MODE);                                                                      \
     }                                                                                                    \
   } while (0)
+  // the diffusion sweeps: fp64 registers for either storage type (dtype "fp32" runs the mixed arithmetic)
+#define PMX_PCG1_DIF(PF)                                                                                 \
+  do {                                                                                                   \
+    if (wsweep)                                                                                          \
+      hipLaunchKernelGGL((k_pcg1<T, double, 2, 1, PF, true, 0, kShiftField, true>), dim3(nb), dim3(bs), tc.lds_pad, s, \
+                         G, Tb, w, r, r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);     \
+    else                                                                                                 \
+      hipLaunchKernelGGL((k_pcg1<T, double, 2, 1, PF, false, 0, kShiftField, true>), dim3(nb), dim3(bs), tc.lds_pad, s, \
+                         G, Tb, w, r, r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);     \
+  } while (0)
+  if (ka) {
+    PMX_CHECK(shift && kb, "pcg1: a diffusion session holds the shift field and both face fields");
+    PMX_CHECK(tc.vec == 2 && tc.waves == 1 && (tc.pf == 1 || tc.pf == 2) && tc.dpf == 0 && !tc.arith32,
+              "pcg1 with a diffusion field runs the default tile shapes (vec 2 x 1 wave, prefetch 1 or 2, no "
+              "LDS-DMA) in fp64 registers");
+    if (tc.pf == 1) PMX_PCG1_DIF(1);
+    else PMX_PCG1_DIF(2);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+#undef PMX_PCG1_DIF
   if (sigma != 0.0 || shift) {
     PMX_CHECK(tc.vec == 2 && tc.waves == 1 && (tc.pf == 1 || tc.pf == 2) && tc.dpf == 0,
               "pcg1 with sigma != 0 or a reaction field runs the default tile shapes (vec 2 x 1 wave, prefetch 1 "
@@ -740,12 +783,13 @@ void* pcg1_wave_trace_setup(long long it, int nwaves) {
 
 template void launch_pcg1<double>(const DevGeom&, const DevTables&, double*, double*, double*, double*,
                                   double*, double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double,
-                                  const double*);
+                                  const double*, const double*, const double*);
 template void launch_pcg1_halo<double>(const DevGeom&, double*, double*, double*, double*, HaloBufs<double>,
                                         long long, bool, hipStream_t, long long*);
 template void launch_pcg1_halo<float>(const DevGeom&, float*, float*, float*, float*, HaloBufs<float>,
                                        long long, bool, hipStream_t, long long*);
 template void launch_pcg1<float>(const DevGeom&, const DevTables&, float*, float*, float*, float*, float*,
-                                 double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double, const float*);
+                                 double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double, const float*,
+                                 const float*, const float*);
 
 }  // namespace pmx

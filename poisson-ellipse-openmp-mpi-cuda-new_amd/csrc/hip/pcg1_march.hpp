@@ -422,13 +422,18 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
 }
 
-template <typename T, int VEC, bool FLD = false>
+// FLD: 0 the rows of every sweep without a field, 1 kShiftField, 2 kShiftField with a diffusion field
+template <typename T, int VEC, int FLD = 0>
 struct Pcg1Row {
   T r[VEC], p[VEC], w[VEC], q[VEC];  // q: p^{k-2} (WM 3 only)
 };
 template <typename T, int VEC>
-struct Pcg1Row<T, VEC, true> {  // kShiftField: + the row's shift values T(sigma + c)
+struct Pcg1Row<T, VEC, 1> {  // kShiftField: + the row's shift values T(sigma + c)
   T r[VEC], p[VEC], w[VEC], q[VEC], s[VEC];
+};
+template <typename T, int VEC>
+struct Pcg1Row<T, VEC, 2> {  // + the x faces of the row BELOW (ak of row m+1) and the row's y faces, with the
+  T r[VEC], p[VEC], w[VEC], q[VEC], s[VEC], a[VEC], b[VEC + 1];  // face of the column after the lane's last
 };
 
 // w schedule of one sweep (template WM of pcg1_march): 0 = w untouched; 1 = pairs, w += c1 p^{k-1}
@@ -461,8 +466,16 @@ struct Pcg1Row<T, VEC, true> {  // kShiftField: + the row's shift values T(sigma
 // pieces at different times (bench/probe/dma_march.hip k_lock: 16384^2, 16 waves per CU, 1.846 ->
 // 1.688 ms per sweep).  Pure pacing: no data passes between the waves, every wave of a workgroup
 // marches the same number of rows (one tile row), and a wave that has left no longer counts.
+//
+// DIF (a session with a diffusion field; on top of SH = kShiftField, fp64 registers): the four faces of a node
+// come from the session's face-coefficient fields ka / kb (geometry and k folded in, InitData::ka / kb) and
+// not from the tables: no row classes, no cut-row path, no parked column constants.  The fetch of row m
+// gains the x-face row m+1 and the y-face row m -- the lane's VEC columns and the column after them, whose
+// face is the right face of the lane's last node (one past what the wave loads, so DPP cannot supply it) --
+// and the rows travel down the stages like Sm1 / Sm2: stage A reads ak(m), ak(m+1), bk(m, .), stage B row
+// m-1, stage C row m-2.  D + s divides through zdiv_field at every call site, as the field sweeps do.
 template <typename T, typename C, int VEC, int PF, int WM, bool FAST, int DPF = 0, bool LOCK = false,
-          int SH = kShiftNone>
+          int SH = kShiftNone, bool DIF = false>
 __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb, const ArithF& F, T* __restrict__ w,
                                            const T* __restrict__ rold, T* __restrict__ rnew,
                                            const T* __restrict__ pold,
@@ -470,11 +483,15 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
                                            double alpha_d, double beta_d, double c1_d, double c2_d,
                                            double (&acc)[kNq], double* __restrict__ scol,
                                            unsigned long long cls, bool use_cls, double* dring = nullptr,
-                                           const T* __restrict__ shf = nullptr) {
+                                           const T* __restrict__ shf = nullptr,
+                                           const T* __restrict__ ka = nullptr,
+                                           const T* __restrict__ kb = nullptr) {
   constexpr bool WUP = WM != 0;
   constexpr bool FLD = SH == kShiftField;  // shf: the subdomain's shift field at local (0, 0), r's layout
   static_assert(!FLD || DPF == 0, "the reaction field runs the register-prefetch march");
-  using Row = Pcg1Row<T, VEC, FLD>;
+  static_assert(!DIF || (FLD && VEC == 2 && std::is_same_v<C, double>),
+                "the diffusion field: a field sweep with 2 columns per lane in fp64 registers");
+  using Row = Pcg1Row<T, VEC, DIF ? 2 : FLD ? 1 : 0>;
   static_assert(DPF == 0 || (FAST && VEC == 2 && sizeof(T) == 8 && WM <= 2), "LDS-DMA march: fp64 FAST tiles, WM 0-2");
   constexpr bool PK = std::is_same_v<C, float> && VEC == 2;  // packed fp32 stencils (apply_row)
   const C alpha = C(alpha_d), beta = C(beta_d), c1 = C(c1_d), c2 = C(c2_d);
@@ -501,6 +518,7 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
   auto grow = [&](int m) { return min(max(G.gi0 + m, 0), G.M); };  // table row of local row m
   // row m's class: from the slot's bits (Pcg1Slot) or from the tables
   auto row_of = [&](int m) {
+    if constexpr (DIF) return RowCo{0, 1};  // unused: no table rows, never the cut path
     if (use_cls) return RowCo{grow(m), int((cls >> (2 * (m - i0 + 3))) & 3ull)};
     return row_co(Tb, grow(m), gjlo, gjhi);
   };
@@ -516,6 +534,14 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
     load_cols<T, VEC>(rold + int64_t(mc) * P, c0, cmax, b.r);
     load_cols<T, VEC>(pold + int64_t(mc) * P, c0, cmax, b.p);
     if constexpr (FLD) load_cols<T, VEC>(shf + int64_t(mc) * P, c0, cmax, b.s);
+    if constexpr (DIF) {  // ak has one more row than r (nx+3); the extra column c + VEC <= cmax + 2 lies in the row
+      load_cols<T, VEC>(ka + int64_t(mc + 1) * P, c0, cmax, b.a);
+      T bt[VEC];
+      load_cols<T, VEC>(kb + int64_t(mc) * P, c0, cmax, bt);
+#pragma unroll
+      for (int u = 0; u < VEC; ++u) b.b[u] = bt[u];
+      b.b[VEC] = *col_ptr(kb + int64_t(mc) * P, min(c0 + VEC - 2, cmax) + 2);
+    }
     if constexpr (WUP) {  // w of the row stage B handles next step
       const int wc = min(max(m - 1, -1), G.nx + 2);
       load_cols<T, VEC>(w + int64_t(wc) * P, c0, cmax, b.w);
@@ -533,6 +559,19 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
   [[maybe_unused]] C Sm1[VEC], Sm2[VEC];
 #pragma unroll
   for (int u = 0; u < VEC; ++u) Sm1[u] = Sm2[u] = C(0);
+  // DIF: the x faces of rows m (stage A's upper face), m-1 and m-2 and the y faces of rows m-1 and m-2; before
+  // the first rows arrive they hold 1, so that no D of a row that is never used is 0
+  [[maybe_unused]] C Aa[VEC], Ab[VEC], Ac[VEC], Bb[VEC + 1], Bc[VEC + 1];
+#pragma unroll
+  for (int u = 0; u < VEC; ++u) Aa[u] = Ab[u] = Ac[u] = C(1);
+#pragma unroll
+  for (int u = 0; u <= VEC; ++u) Bb[u] = Bc[u] = C(1);
+  if constexpr (DIF) {  // ak of the first marched row (i0 - 2 >= -1)
+    T at[VEC];
+    load_cols<T, VEC>(ka + int64_t(i0 - 2) * P, c0, cmax, at);
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) Aa[u] = C(at[u]);
+  }
   RowCo cB = row_of(i0 - 3);  // rows m-1, m-2
   RowCo cC = cB;
   bool parked = false;  // column constants in LDS (see col_lds)
@@ -566,7 +605,11 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       rom[u] = in ? C(cur.r[u]) : C(0);
       pom[u] = in ? C(cur.p[u]) : C(0);
       C a0, a1, b0, b1;
-      coef_c<C>(cA, Tb, G, F, scol, u, lane, gj[u], a0, a1, b0, b1);
+      if constexpr (DIF) {
+        a0 = Aa[u]; a1 = C(cur.a[u]); b0 = C(cur.b[u]); b1 = C(cur.b[u + 1]);
+      } else {
+        coef_c<C>(cA, Tb, G, F, scol, u, lane, gj[u], a0, a1, b0, b1);
+      }
       const C z = zdiv_c<C, SH>(cA.ucls, rom[u], a0, a1, b0, b1, G, F, sm[u]);
       const C v = fma_c(beta, pom[u], z);
       Pm[u] = in ? C(static_cast<T>(v)) : C(0);  // the stored (rounded) p^k is the one used
@@ -599,8 +642,12 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       }
 #pragma unroll
       for (int u = 0; u < VEC; ++u) {
-        if constexpr (!PK) {
+        if constexpr (DIF) {
+          a0[u] = Ab[u]; a1[u] = Aa[u]; b0[u] = Bb[u]; b1[u] = Bb[u + 1];
+        } else if constexpr (!PK) {
           coef_at(cB, mb, u, a0[u], a1[u], b0[u], b1[u]);
+        }
+        if constexpr (!PK) {
           Ap[u] = apply_c<C, SH>(Pm1[u], Pm2[u], Pm[u], u == 0 ? left : Pm1[u - 1],
                              u == VEC - 1 ? right : Pm1[u + 1], a0[u], a1[u], b0[u], b1[u], G, F, Sm1[u]);
           if constexpr (WM == 2)
@@ -651,8 +698,12 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       }
 #pragma unroll
       for (int u = 0; u < VEC; ++u) {
-        if constexpr (!PK) {
+        if constexpr (DIF) {
+          a0[u] = Ac[u]; a1[u] = Ab[u]; b0[u] = Bc[u]; b1[u] = Bc[u + 1];
+        } else if constexpr (!PK) {
           coef_at(cC, mcr, u, a0[u], a1[u], b0[u], b1[u]);
+        }
+        if constexpr (!PK) {
           Az[u] = apply_c<C, SH>(Zm2[u], Zm3[u], Zm1[u], u == 0 ? left : Zm2[u - 1],
                              u == VEC - 1 ? right : Zm2[u + 1], a0[u], a1[u], b0[u], b1[u], G, F, Sm2[u]);
         }
@@ -673,6 +724,16 @@ __device__ __forceinline__ void pcg1_march(const DevGeom& G, const DevTables& Tb
       if constexpr (FLD) {
         Sm2[u] = Sm1[u];
         Sm1[u] = sm[u];
+      }
+      if constexpr (DIF) {
+        Ac[u] = Ab[u]; Ab[u] = Aa[u]; Aa[u] = C(cur.a[u]);
+      }
+    }
+    if constexpr (DIF) {
+#pragma unroll
+      for (int u = 0; u <= VEC; ++u) {
+        Bc[u] = Bb[u];
+        Bb[u] = C(cur.b[u]);
       }
     }
     cC = cB;

@@ -57,6 +57,8 @@ TileCfg make_tiles(const DevGeom& G, int block, int rows) {
 // (z0, r0) partial, in every mode; sigma is InitData's last member, and the launchers pick SH from it.
 // SH = 2 (a session with a reaction field): the node's own shift T(sigma + c) from X.shift -- the
 // subdomain's shift field, r's layout -- in place of X.sigma, in the same two places and in rho_B.
+// SH = 3 (a session with a diffusion field): as 2, and the four faces of the node come from the session's
+// face-coefficient fields X.ka / X.kb (ak(i), ak(i+1), bk(j), bk(j+1)) instead of the 1-D tables.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double resid(double B, double Aw) {
   PMX_NO_CONTRACT
@@ -95,12 +97,18 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
     }
     for (int i = t.i0; i <= t.iend; ++i) {
       const int gi = G.gi0 + i;
-      const RowConst rc = load_row(Tb, gi);
-      const double a0 = face_a(cc, rc.rv0, G), a1 = face_a(cc, rc.rv1, G);
-      const double b0 = face_b(rc, cc.rh0, G), b1 = face_b(rc, cc.rh1, G);
       const int64_t c = int64_t(i) * P + j;
+      double a0, a1, b0, b1;
+      if constexpr (SH == 3) {
+        a0 = double(X.ka[c]); a1 = double(X.ka[c + P]);
+        b0 = double(X.kb[c]); b1 = double(X.kb[c + 1]);
+      } else {
+        const RowConst rc = load_row(Tb, gi);
+        a0 = face_a(cc, rc.rv0, G); a1 = face_a(cc, rc.rv1, G);
+        b0 = face_b(rc, cc.rh0, G); b1 = face_b(rc, cc.rh1, G);
+      }
       [[maybe_unused]] double sg = X.sigma;
-      if constexpr (SH == 2) sg = double(X.shift[c]);
+      if constexpr (SH >= 2) sg = double(X.shift[c]);
       // B_ij = F inside D (stage0/Withoutopenmp1.cpp:60)
       const bool in = geo::inside(Tb.x[gi], yj, G.ax, G.by, G.ref_ellipse != 0);
       T Bs;
@@ -288,8 +296,18 @@ __global__ void k_local_allreduce(double* const* bufs, int nranks, int nq) {
 
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
-                 double* partials, const TileCfg& tc, hipStream_t s, double sigma, const T* shift) {
-  if (shift) {
+                 double* partials, const TileCfg& tc, hipStream_t s, double sigma, const T* shift, const T* ka,
+                 const T* kb) {
+  if (ka) {
+    PMX_CHECK(shift && kb, "k_init: a diffusion session holds the shift field and both face fields");
+    InitData<T> X;
+    X.shift = shift;
+    X.ka = ka;
+    X.kb = kb;
+    PMX_BLOCK_DISPATCH(tc.block,
+        hipLaunchKernelGGL((k_init<T, B, kInitPlain, 3>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
+                           partials, tc.rows, tc.tiles_j, X));
+  } else if (shift) {
     InitData<T> X;
     X.shift = shift;
     PMX_BLOCK_DISPATCH(tc.block,
@@ -319,7 +337,13 @@ void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBuf
                       const TileCfg& tc, const InitData<T>& X, bool measure, hipStream_t s) {
   PMX_CHECK(tc.block == 256, "the data init runs the init tiling (256 columns per tile)");
   const bool sh = X.sigma != 0.0;
-  if (measure && X.shift)
+  if (measure && X.ka)
+    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, 3>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+                       partials, tc.rows, tc.tiles_j, X);
+  else if (X.ka)
+    hipLaunchKernelGGL((k_init<T, 256, kInitData, 3>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
+                       partials, tc.rows, tc.tiles_j, X);
+  else if (measure && X.shift)
     hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, 2>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
                        partials, tc.rows, tc.tiles_j, X);
   else if (X.shift)
@@ -370,7 +394,7 @@ void launch_local_allreduce(double* const* bufs, int nranks, int nq, hipStream_t
 
 #define PMX_INST(T)                                                                              \
   template void launch_init<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>, double*,  \
-                               const TileCfg&, hipStream_t, double, const T*);                   \
+                               const TileCfg&, hipStream_t, double, const T*, const T*, const T*); \
   template void launch_init_data<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>,       \
                                     double*, const TileCfg&, const InitData<T>&, bool,           \
                                     hipStream_t);                                                 \

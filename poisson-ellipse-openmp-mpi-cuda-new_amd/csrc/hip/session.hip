@@ -51,10 +51,22 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
                                   "local communicator); multi-process transports are not supported");
     pre.reaction = 1;
   }
+  UserField dif(cfg_.diffusion);
+  dif.ld = cfg_.diffusion_ld;
+  dif.on_device = cfg_.diffusion_on_device;
+  dif.stream = cfg_.diffusion_stream;
+  if (dif) {
+    if (cfg_.comm != CommKind::kSelf && cfg_.comm != CommKind::kLocal)
+      throw std::invalid_argument("a diffusion field needs a session that owns every subdomain (world 1 or the "
+                                  "local communicator); multi-process transports are not supported");
+    pre.reaction = 1;  // the field state of the shift switch: T(sigma + c), c = 0 without a reaction field
+    pre.diffusion = 1;
+  }
   GpuOptions base = resolve_options(pre);
   // sigma != 0 or a reaction field: pcg1 on the row march, or std::invalid_argument
   apply_sigma_rules(cfg_.spec, pg_, base);
   if (react) check_reaction(react);  // before anything is allocated
+  if (dif) check_diffusion(dif);
   if (base.algo == -1) {
     HIP_CHECK(hipSetDevice(cfg_.devices[0]));
     size_t free_b = 0, total_b = 0;
@@ -73,6 +85,13 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
     solvers_.push_back(std::make_unique<GpuSubdomainSolver>(cfg_.spec, sd, o));
   }
   if (react) upload_reaction(react);
+  if (dif) {
+    if (!react) {  // the shift field of a diffusion session without a reaction field: T(sigma)
+      const std::vector<double> zero(size_t(cfg_.spec.M + 1) * size_t(cfg_.spec.N + 1), 0.0);
+      upload_reaction(UserField(zero.data()));
+    }
+    upload_diffusion(dif);
+  }
   if (!cfg_.defer_connect) connect();
 }
 
@@ -257,7 +276,77 @@ void Session::set_reaction(const UserField& c) {
   stale_ = true;
 }
 
+void Session::check_diffusion(const UserField& k) const {
+  const int M = cfg_.spec.M, N = cfg_.spec.N;
+  const int64_t ld = k.ld ? k.ld : N + 1;
+  if (ld < N + 1) throw std::invalid_argument("diffusion: row stride below N + 1");
+  bool bad = false;
+  if (k.on_device) {
+    for (int d : cfg_.devices)
+      if (d != cfg_.devices[0])
+        throw std::invalid_argument("a device diffusion field needs every subdomain of the session on its device");
+    HIP_CHECK(hipSetDevice(cfg_.devices[0]));
+    int* flag = nullptr;  // for the call only
+    int h = 0;
+    HIP_CHECK(hipMalloc(&flag, sizeof(int)));
+    try {
+      HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), k.stream));
+      launch_diffusion_check(k.ptr, ld, M + 1, N + 1, flag, k.stream);  // every node
+      HIP_CHECK(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, k.stream));
+      HIP_CHECK(hipStreamSynchronize(k.stream));
+    } catch (...) {
+      (void)hipStreamSynchronize(k.stream);
+      (void)hipFree(flag);
+      throw;
+    }
+    HIP_CHECK(hipFree(flag));
+    bad = h != 0;
+  } else {
+    for (int i = 0; i <= M && !bad; ++i)
+      for (int j = 0; j <= N; ++j) {
+        const double v = k.ptr[int64_t(i) * ld + j];
+        if (!(v > 0.0) || std::isinf(v)) {
+          bad = true;
+          break;
+        }
+      }
+  }
+  if (bad) throw std::invalid_argument("diffusion must be finite and > 0 on every node");
+}
+
+void Session::upload_diffusion(const UserField& k) {
+  const int M = cfg_.spec.M, N = cfg_.spec.N;
+  const int64_t ld = k.ld ? k.ld : N + 1;
+  for (auto& sp : solvers_) {
+    if (k.on_device) {  // on its producer's stream; the solver returns once that stream has consumed the field
+      sp->set_diffusion(k.ptr, ld, k.stream);
+      continue;
+    }
+    HIP_CHECK(hipSetDevice(sp->device()));
+    double* raw = nullptr;  // for this subdomain's kernel only
+    HIP_CHECK(hipMalloc(&raw, size_t(M + 1) * size_t(N + 1) * sizeof(double)));
+    const DevPtr<double> tmp(raw);
+    HIP_CHECK(hipMemcpy2D(tmp.get(), size_t(N + 1) * sizeof(double), k.ptr, size_t(ld) * sizeof(double),
+                          size_t(N + 1) * sizeof(double), size_t(M + 1), hipMemcpyHostToDevice));
+    sp->set_diffusion(tmp.get(), N + 1, nullptr);
+  }
+}
+
+void Session::set_diffusion(const UserField& k) {
+  if (!has_diffusion())
+    throw std::invalid_argument("set_diffusion needs a session built with a diffusion field (make_session(p, "
+                                "diffusion=k)): sessions without one hold no face-coefficient fields");
+  if (!k) throw std::invalid_argument("set_diffusion: no field given");
+  check_diffusion(k);
+  if (!drivers_.empty()) synchronize();  // no sweep in flight reads the fields
+  upload_diffusion(k);
+  stale_ = true;
+}
+
 ErrorStats Session::error_norms() {
+  if (has_diffusion())
+    throw std::invalid_argument("error_norms: the closed-form solution does not solve a problem with a diffusion "
+                                "field; compare the solution with your own (PoissonEllipse.error_norms(w, exact=u))");
   if (has_reaction())
     throw std::invalid_argument("error_norms: the closed-form solution does not solve a problem with a reaction "
                                 "field; compare the solution with your own (PoissonEllipse.error_norms(w, exact=u))");
@@ -446,7 +535,11 @@ void Session::apply_device(const UserField& x, const UserField& out, const UserF
   K.alpha = alpha; K.beta = beta; K.gamma = y ? gamma : 0.0; K.c0 = c0; K.sigma = cfg_.spec.sigma;
   K.plain = alpha == 1.0 && beta == 0.0 && !y && c0 == 0.0;
   for (size_t i = 0; i < solvers_.size(); ++i) {
-    if (has_reaction()) {  // the owning subdomain's shift field, in sigma's place
+    if (has_diffusion()) {  // ... and its face-coefficient fields, in the tables' place
+      K.ka = solvers_[i]->face_base(0);
+      K.kb = solvers_[i]->face_base(1);
+    }
+    if (has_reaction() || has_diffusion()) {  // the owning subdomain's shift field, in sigma's place
       K.shift = solvers_[i]->shift_base();
       K.spitch = solvers_[i]->pitch();
       K.sgi0 = solvers_[i]->sd().gi0();
@@ -464,7 +557,8 @@ void Session::apply_device(const UserField& x, const UserField& out, const UserF
 }
 
 void Session::step(int64_t n) {
-  PMX_CHECK(!stale_, "step: the reaction field changed (set_reaction) since the last init; call init() or solve()");
+  PMX_CHECK(!stale_, "step: the reaction or diffusion field changed (set_reaction / set_diffusion) since the last "
+                     "init; call init() or solve()");
   for_drivers([n](size_t, PcgDriver& d) { d.enqueue_iterations(n); });
 }
 
@@ -482,7 +576,8 @@ RunStats Session::solve_impl(int poll_batches, bool do_init, int64_t every, cons
   // identical everywhere); rank 0's statistics are returned
   std::vector<RunStats> st(drivers_.size());
   if (do_init) stale_ = false;
-  PMX_CHECK(!stale_, "the reaction field changed (set_reaction) since the last init; call init() or solve()");
+  PMX_CHECK(!stale_, "the reaction or diffusion field changed (set_reaction / set_diffusion) since the last init; "
+                     "call init() or solve()");
   for_drivers([&](size_t i, PcgDriver& d) {
     std::function<void(const PcgState&)> cb;
     if (every > 0 && !save_path.empty()) {
@@ -556,6 +651,9 @@ std::vector<double> Session::gather_local_w() {
 }
 
 void Session::require_no_sigma(const char* what) const {
+  if (has_diffusion())
+    throw std::invalid_argument(std::string(what) + ": checkpoint files do not record a diffusion field (format "
+                                "v7); sessions with one cannot be checkpointed");
   if (has_reaction())
     throw std::invalid_argument(std::string(what) + ": checkpoint files do not record a reaction field (format "
                                 "v7); sessions with one cannot be checkpointed");

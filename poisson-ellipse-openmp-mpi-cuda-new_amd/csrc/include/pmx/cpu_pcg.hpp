@@ -37,8 +37,14 @@ struct SolveResult {
 // reaction: optional global field c(x, y) >= 0 next to spec.sigma: the operator is A + (sigma + c) I and the
 // Jacobi diagonal D + sigma + c on every interior node (boundary values are not read).  The shift enters
 // through the one expression sigma uses, so a constant field equals the sigma solve bitwise.
+// diffusion: optional global field k(x, y) of nodal values, finite and > 0 on EVERY node (the faces next to the
+// box boundary read its boundary values): the operator is -div(k grad u) + (sigma + c) u, with the face
+// coefficients a[i,j] <- (0.5 (k[i-1,j] + k[i,j])) a[i,j], b[i,j] <- (0.5 (k[i,j-1] + k[i,j])) b[i,j] -- the
+// fictitious coefficient 1/eps included, so the medium outside D is k/eps -- and everything else the same
+// algebra on them.  k = 1 multiplies by exactly 1.0: the solve without the argument, bitwise.
 SolveResult cpu_solve(const ProblemSpec& spec, int threads = 1, bool keep_solution = true,
-                      const double* rhs = nullptr, const double* w0 = nullptr, const double* reaction = nullptr);
+                      const double* rhs = nullptr, const double* w0 = nullptr, const double* reaction = nullptr,
+                      const double* diffusion = nullptr);
 
 // Assemble the reference's 2D arrays on the host (tests: kernel bit-equality).
 // a, b are (M+2) x (N+2) including ghost nodes; B is (M+1) x (N+1).
@@ -50,16 +56,18 @@ void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<d
 // matrix on the whole box, no ellipse mask -- in cpu_solve's mat_A arithmetic.  Boundary values of x count as 0
 // and are not read; y may be null (no y term).  Combination order: v = alpha Lx; v = fma(beta, x, v);
 // v = fma(gamma, y, v) with y; v += c0 -- and Lx itself for alpha = 1, beta = 0, no y, c0 = 0.
-// reaction: as cpu_solve (L = A + (sigma + c) I).
+// reaction, diffusion: as cpu_solve (L = A_k + (sigma + c) I).
 std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const double* y = nullptr, double alpha = 1.0,
-                              double beta = 0.0, double gamma = 1.0, double c0 = 0.0, const double* reaction = nullptr);
+                              double beta = 0.0, double gamma = 1.0, double c0 = 0.0, const double* reaction = nullptr,
+                              const double* diffusion = nullptr);
 
 // One rank's block (local arrays (nx+2) x (ny+2), row-major, pitch ny+2).
 class CpuSubdomain {
  public:
-  // rhs / w0 / reaction: as cpu_solve (global arrays; this block, and for w0 its ring, are copied)
+  // rhs / w0 / reaction / diffusion: as cpu_solve (global arrays; this block, and for w0 its ring, are copied;
+  // diffusion is folded into the block's face coefficients)
   CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads, const double* rhs = nullptr,
-               const double* w0 = nullptr, const double* reaction = nullptr);
+               const double* w0 = nullptr, const double* reaction = nullptr, const double* diffusion = nullptr);
 
   const Subdomain& sd() const { return sd_; }
   int pitch() const { return sd_.ny + 2; }
@@ -98,7 +106,7 @@ class CpuSubdomain {
 SolveResult cpu_solve_decomposed(const ProblemSpec& spec, int nranks, Split split,
                                  int threads_per_rank = 1, bool keep_solution = true,
                                  const double* rhs = nullptr, const double* w0 = nullptr,
-                                 const double* reaction = nullptr);
+                                 const double* reaction = nullptr, const double* diffusion = nullptr);
 
 // Generic lock-step PCG over CpuSubdomains with pluggable collectives.  The MPI
 // app supplies MPI-backed callbacks; the in-process driver supplies local ones.

@@ -173,6 +173,11 @@ struct GpuOptions {
   // field T(sigma + c) (MemoryPlan::nshift) and runs the field state of the shift switch, under the rules of
   // the screened problem (apply_sigma_rules).  Set by the Session; the values arrive through set_reaction.
   int reaction = 0;
+  // The session solves with a diffusion field k(x, y) (Session's `diffusion`): every solver allocates the two
+  // face-coefficient fields (MemoryPlan::ndiff) next to the shift field -- a diffusion session always runs
+  // the field state of the shift switch, so `reaction` is set with it -- and runs the diffusion sweeps, in
+  // fp64 registers for either storage type.  Set by the Session; the values arrive through set_diffusion.
+  int diffusion = 0;
   bool resolved = false;  // environment overrides already applied (resolve_options)
 };
 
@@ -298,6 +303,15 @@ class GpuSubdomainSolver {
   // The iteration state belongs to the old operator afterwards: the next init starts the new one.
   void set_reaction(const double* c, int64_t ld, bool on_device, hipStream_t s);
   bool has_reaction() const { return plan_.nshift != 0; }
+  // Solvers built with GpuOptions::diffusion: (re)fill the face-coefficient fields from the nodal values k, a
+  // global (M+1) x (N+1) fp64 array in memory of this solver's device (row stride ld), by one kernel on s
+  // (launch_face_fields: this subdomain's block with its radius-2 frame plus the extra row and column; cells
+  // beyond the box hold 1).  Returns after s has consumed k.  Addresses never change, the values are static
+  // and nothing is exchanged, as set_reaction.
+  void set_diffusion(const double* k, int64_t ld, hipStream_t s);
+  bool has_diffusion() const { return plan_.ndiff != 0; }
+  // the face-coefficient fields (f: 0 ak, 1 bk) at local (0, 0) in the storage type; nullptr without
+  const void* face_base(int f) const { return plan_.ndiff ? field_ptr(plan_.diff_field(f)) : nullptr; }
   // the shift field at local (0, 0) in the storage type; nullptr without a reaction field
   const void* shift_base() const { return plan_.nshift ? field_ptr(plan_.shift_field()) : nullptr; }
   int64_t pitch() const { return plan_.pitch; }
@@ -471,6 +485,7 @@ class GpuSubdomainSolver {
     return {at(0), at(1), plan_.nfields == 5 ? at(4) : nullptr, at(2), at(3)};
   }
   template <typename T> const T* shift() const { return static_cast<const T*>(shift_base()); }
+  template <typename T> const T* face(int f) const { return static_cast<const T*>(face_base(f)); }
   template <typename T> HaloBufs<T> halo() const;
   template <typename T> void init_impl(hipStream_t s);
   template <typename T> void kernel_a(hipStream_t s, int part = 0);  // k_pcg_a, or the pcg1 sweep

@@ -85,7 +85,8 @@ enum AblBits : int {
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
                  double* partials, const TileCfg& tc, hipStream_t s, double sigma = 0.0,
-                 const T* shift = nullptr);  // shift: as InitData::shift
+                 const T* shift = nullptr,  // shift: as InitData::shift
+                 const T* ka = nullptr, const T* kb = nullptr);  // as InitData::ka / kb
 
 // k_init with data (GpuSubdomainSolver::set_init_data / residual_norm), on launch_init's tiling.
 //   data init (measure = false): r holds f on the owned nodes (has_f; else the constant G.F), w holds
@@ -112,6 +113,12 @@ struct InitData {
   // a session with a reaction field: its shift field T(sigma + c) at local (0, 0), the fields' layout; non-null
   // launches the kernels that read the node's own shift instead of sigma
   const T* shift = nullptr;
+  // a session with a diffusion field (it always holds a shift field too): its complete face-coefficient fields
+  // ak(i, j) -- the face between nodes (i-1, j) and (i, j) -- and bk(i, j) -- between (i, j-1) and (i, j) --
+  // at local (0, 0), the fields' layout; non-null launches the kernels that read the four faces of a node from
+  // them instead of forming them from the 1-D tables
+  const T* ka = nullptr;
+  const T* kb = nullptr;
 };
 template <typename T>
 void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
@@ -156,7 +163,9 @@ template <typename T>
 void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0, T* p1,
                  double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part = 0,
                  bool wsweep = false, double sigma = 0.0,  // sigma: ProblemSpec::sigma (!= 0: the SH sweeps)
-                 const T* shift = nullptr);  // the shift field of a reaction session (the field sweeps), else null
+                 const T* shift = nullptr,  // the shift field of a reaction session (the field sweeps), else null
+                 // the face-coefficient fields of a diffusion session (the diffusion sweeps; with shift), else null
+                 const T* ka = nullptr, const T* kb = nullptr);
 
 // pcg1 sweep with block tiles (pcg1_block.hip): one workgroup per tc.rows x 124 tile, the three
 // pipeline stages row-parallel; undecomposed fp64 grids; partial sums per tile as k_pcg1.  With a ticket the sweep also finishes the reduction (red_c =
@@ -321,6 +330,16 @@ template <typename T>
 void launch_scatter_shift(const double* src, int64_t ld, T* dst, int64_t pitch, int rows, int cols, double sigma,
                           hipStream_t s);
 void launch_reaction_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s);
+// A diffusion field (io_kernels.hip).  The check of its values: *flag <- 1 for a NaN, an infinity or a value
+// <= 0 among the rows x cols values.  And the face-coefficient fields of one subdomain from the nodal values
+// k (global (M+1) x (N+1), row stride ld, device memory) and the 1-D tables:
+//   ak(li, lj) = T((0.5 (k[gi-1, gj] + k[gi, gj])) a(gi, gj)),  bk(li, lj) = T((0.5 (k[gi, gj-1] + k[gi, gj])) b(gi, gj))
+// in fp64, rounded once, with a / b the exact face formulas (coef_a / coef_b, as the s-step's face fields);
+// faces that do not lie between two nodes of the box get 1.  ak, bk point to local (0, 0), row stride
+// G.pitch; written: local rows -1 .. nx+3 of ak, -1 .. nx+2 of bk, columns -1 .. G.pitch-2 (the whole row).
+template <typename T>
+void launch_face_fields(const DevGeom& G, const DevTables& Tb, const double* k, int64_t ld, T* ak, T* bk, hipStream_t s);
+void launch_diffusion_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s);
 // local nodes (li0 .. li0+rows-1) x (lj0 .. lj0+cols-1) of a subdomain with local (0, 0) at global
 // (gi0, gj0) -> out[gi * ld + gj]: w + ca pa (+ cb pb) as launch_error_norms forms it (w, pa, pb point to
 // local (0, 0), row stride pitch); nodes on the global boundary (gi in {0, M}, gj in {0, N}) get zero
@@ -344,6 +363,10 @@ struct ApplyCoef {
   const void* shift = nullptr;
   int64_t spitch = 0;
   int sgi0 = 0, sgj0 = 0, selem = 8;
+  // a session with a diffusion field: the owning subdomain's face-coefficient fields (InitData::ka / kb), in
+  // the shift field's layout and element type; read in place of the faces from the tables.  Null: the tables.
+  const void* ka = nullptr;
+  const void* kb = nullptr;
 };
 void launch_apply(const DevGeom& G, const DevTables& Tb, const double* x, int64_t ldx, const double* y, int64_t ldy,
                   double* out, int64_t ldo, int gi_lo, int gj_lo, int rows, int cols, const ApplyCoef& K,

@@ -28,13 +28,20 @@ struct MemoryPlan {
   // with r's pitch and ghost layers, behind the nfields iteration fields (index shift_field()).  0 without:
   // every other plan is what it was.
   int nshift = 0;
+  // The face-coefficient fields of a session with a diffusion field: two more fields behind the shift field,
+  // bk (index diff_field(1)) and then ak (diff_field(0)) -- ak last, because the x faces need one more row
+  // than r's layout (local rows -1 .. nx+3: stage A of the march on ghost row nx+2 reads ak of row nx+3);
+  // that row is diff_extra bytes behind the last field.  0 without: every other plan is what it was.
+  int ndiff = 0;
+  size_t diff_extra = 0;
 
   MemoryPlan() = default;
   // algo: 1 pcg1, 2 pcg2, 3 the s-step PCG (GpuOptions::algo); ghost_rows: 2, or the s-step's s / 2s on
   // decomposed grids -- rows, and columns on 2-D blocks
-  MemoryPlan(const ProblemSpec& spec, const Subdomain& sd, DType dtype, int algo, int ghost_rows, bool shift = false)
+  MemoryPlan(const ProblemSpec& spec, const Subdomain& sd, DType dtype, int algo, int ghost_rows, bool shift = false,
+             bool diffusion = false)
       : elem(dtype == DType::kFp64 ? 8 : 4), align(256 / elem), gh(ghost_rows), nfields(algo == 1 || algo == 3 ? 5 : 4),
-        nshift(shift ? 1 : 0) {
+        nshift(shift || diffusion ? 1 : 0), ndiff(diffusion ? 2 : 0) {
     const auto round_up = [](size_t x, size_t a) { return (x + a - 1) / a * a; };
     const bool ca = algo == 3;
     // +8 columns of padding: vector loads of VEC <= 4 columns starting at <= ny+3 stay in the row, and the
@@ -51,12 +58,15 @@ struct MemoryPlan {
       face_off = size_t(gh - 1) * size_t(pitch) + 31;
       face_bytes = round_up((31 + rows) * 8, 256);
     }
+    if (ndiff) diff_extra = round_up(size_t(pitch) * elem, 256);
     table_bytes = (4 * size_t(spec.M + 2) + 4 * size_t(spec.N + 2)) * sizeof(double) +
                   8 * size_t(spec.M + 2) * sizeof(int);
   }
 
-  size_t fields_total() const { return size_t(nfields + nshift) * field_bytes; }
+  size_t fields_total() const { return size_t(nfields + nshift + ndiff) * field_bytes + diff_extra; }
   int shift_field() const { return nshift ? nfields : -1; }  // at()'s index of the shift field, -1: none
+  // at()'s index of a face-coefficient field (f: 0 ak, 1 bk), -1: none
+  int diff_field(int f) const { return ndiff ? nfields + nshift + (f == 0 ? 1 : 0) : -1; }
   size_t faces_total() const { return 2 * face_bytes; }
   size_t total() const { return fields_total() + faces_total() + table_bytes; }
   size_t row_bytes() const { return size_t(pitch) * elem; }

@@ -46,6 +46,15 @@ struct SessionConfig {
   int64_t reaction_ld = 0;
   bool reaction_on_device = false;
   hipStream_t reaction_stream = nullptr;
+  // Diffusion field k(x, y): the session solves (-div(k grad) + sigma + c) u = f.  Nodal values, a global
+  // (M+1) x (N+1) fp64 array like `reaction`, but finite and > 0 on EVERY node: the faces next to the box
+  // boundary read the boundary values.  Every subdomain keeps the two face-coefficient fields
+  // (GpuSubdomainSolver::set_diffusion) and the shift field (filled with sigma when there is no reaction
+  // field).  The rules and refusals of `reaction` apply.
+  const double* diffusion = nullptr;
+  int64_t diffusion_ld = 0;
+  bool diffusion_on_device = false;
+  hipStream_t diffusion_stream = nullptr;
 };
 
 // A global (M+1) x (N+1) fp64 field handed to a session: host memory, or memory of the session's
@@ -116,6 +125,11 @@ class Session {
   // state belongs to the old operator afterwards: step() throws until the next init() / solve().
   void set_reaction(const UserField& c);
   bool has_reaction() const { return cfg_.reaction != nullptr; }
+  // Replace the diffusion field of a session built with one (SessionConfig::diffusion): as set_reaction --
+  // checked before the session is touched, the face-coefficient fields rewritten in place, step() throws
+  // until the next init() / solve().
+  void set_diffusion(const UserField& k);
+  bool has_diffusion() const { return cfg_.diffusion != nullptr; }
   void step(int64_t n);
   void synchronize();
   RunStats solve(int poll_batches = 1);
@@ -183,6 +197,12 @@ class Session {
   // k_reaction_check launch on its producer's stream)
   void check_reaction(const UserField& c) const;
   void upload_reaction(const UserField& c);
+  // throws std::invalid_argument unless k is finite and > 0 on every node (a device field: one
+  // k_diffusion_check launch over the whole tensor on its producer's stream)
+  void check_diffusion(const UserField& k) const;
+  // a host field goes up whole to a temporary device copy per subdomain, so that one kernel forms the face
+  // fields from either source (the same bits)
+  void upload_diffusion(const UserField& k);
   bool stale_ = false;  // set_reaction since the last init: the iteration state is the old operator's
 
   SessionConfig cfg_;

@@ -174,6 +174,17 @@ class PoissonEllipse:
             raise ValueError(f"{name} must be finite and >= 0 on every interior node")
         return np.ascontiguousarray(a)
 
+    def diffusion_field(self, k, name: str = "diffusion") -> Optional[np.ndarray]:
+        """A diffusion field k(x, y) as a C-contiguous float64 (M+1)x(N+1) array, or None: field()'s type, dtype
+        and shape rules; finite and > 0 on EVERY node -- the faces next to the box boundary read the boundary
+        values (ValueError otherwise; the native entry points apply the same rules)."""
+        if k is None:
+            return None
+        a = self._host_array(k, name)
+        if not (np.isfinite(a).all() and (a > 0).all()):
+            raise ValueError(f"{name} must be finite and > 0 on every node")
+        return np.ascontiguousarray(a)
+
     def _host_array(self, a, name: str, writable: bool = False) -> np.ndarray:
         """field()'s type, dtype and shape rules without its finiteness scan (apply's arguments)."""
         if hasattr(a, "numpy") and hasattr(a, "device"):  # a torch tensor
@@ -192,7 +203,7 @@ class PoissonEllipse:
         return a
 
     def apply(self, x, out=None, *, alpha: float = 1.0, beta: float = 0.0, y=None, gamma: float = 1.0,
-              const: float = 0.0, reaction=None) -> np.ndarray:
+              const: float = 0.0, reaction=None, diffusion=None) -> np.ndarray:
         """alpha L x + beta x + gamma y + const on the interior nodes and 0 on the box boundary, on the host
         (the CPU oracle's stencil); L = A + sigma I with this problem's sigma, the plain matrix on the whole
         box -- fictitious region included, no ellipse mask.  The host twin of Session.apply: NumPy arrays
@@ -201,9 +212,13 @@ class PoissonEllipse:
         non-finite values: a NaN propagates to the nodes whose stencil reads it.
 
         reaction: optional field c(x, y) >= 0 (reaction_field()'s rules): L = A + (sigma + c) I, the operator of
-        a session built with that field."""
+        a session built with that field.
+
+        diffusion: optional nodal field k(x, y) > 0 (diffusion_field()'s rules): A becomes -div(k grad .) with
+        the face coefficients (0.5 (k + k')) a, (0.5 (k + k')) b of the two nodes of a face."""
         xa = self._host_array(x, "x")
         ca = self.reaction_field(reaction)
+        ka = self.diffusion_field(diffusion)
         ya = None if y is None else self._host_array(y, "y")
         oa = None if out is None else self._host_array(out, "out", writable=True)
         for name, v in (("alpha", alpha), ("beta", beta), ("gamma", gamma), ("const", const)):
@@ -213,7 +228,7 @@ class PoissonEllipse:
             raise ValueError("out overlaps x")
         r = _native().cpu_apply(self.to_native(), np.ascontiguousarray(xa),
                                 None if ya is None else np.ascontiguousarray(ya), float(alpha), float(beta),
-                                float(gamma), float(const), reaction=ca)
+                                float(gamma), float(const), reaction=ca, diffusion=ka)
         if oa is None:
             return r
         oa[...] = r

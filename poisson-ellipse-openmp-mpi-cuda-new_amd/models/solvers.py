@@ -65,7 +65,13 @@ def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
     reaction (every backend): an (M+1)x(N+1) float64 field c(x, y), finite and >= 0 on the interior nodes (its
     box-boundary values are ignored and never read): the solve is (-Δ + σ + c) u = f, with D + σ + c as the
     Jacobi diagonal.  hip runs it under sigma's rules (pcg1 on the row march; ValueError for algo="ca" / "pcg2",
-    exact=True, block_tiles=1) and also takes a float64 tensor on its device; see make_session."""
+    exact=True, block_tiles=1) and also takes a float64 tensor on its device; see make_session.
+
+    diffusion (every backend): an (M+1)x(N+1) float64 field k(x, y) of nodal values, finite and > 0 on EVERY node
+    (the faces next to the box boundary read its boundary values): the solve is (-∇·k∇ + σ + c) u = f.  The face
+    coefficients become (0.5 (k[i-1,j] + k[i,j])) a[i,j] and (0.5 (k[i,j-1] + k[i,j])) b[i,j] -- the fictitious
+    1/ε included, so the medium outside D is k/ε -- and D, A x and the stop rules are the same algebra on them.
+    k = 1 is the solve without the argument, bitwise on the CPU backends.  hip: under reaction's rules."""
     if backend in ("cpu", "serial"):
         return solve_cpu(problem, threads=1, **kw)
     if backend in ("omp", "openmp"):
@@ -88,19 +94,19 @@ def _residual_extra(r) -> dict:
 
 
 def solve_cpu(problem: PoissonEllipse, threads: int = 1, keep_solution: bool = True, rhs=None, w0=None,
-              reaction=None) -> Result:
+              reaction=None, diffusion=None) -> Result:
     r = _native().cpu_solve(problem.to_native(), int(threads), bool(keep_solution), rhs=rhs, w0=w0,
-                            reaction=reaction)
+                            reaction=reaction, diffusion=diffusion)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
                   backend="cpu" if threads <= 1 else f"omp{threads}", extra=_residual_extra(r))
 
 
 def solve_cpu_decomposed(problem: PoissonEllipse, ranks: int = 4, split: str = "reference",
                          threads: int = 1, keep_solution: bool = True, rhs=None, w0=None,
-                         reaction=None) -> Result:
+                         reaction=None, diffusion=None) -> Result:
     n = _native()
     r = n.cpu_solve_decomposed(problem.to_native(), int(ranks), getattr(n.Split, split), int(threads),
-                               bool(keep_solution), rhs=rhs, w0=w0, reaction=reaction)
+                               bool(keep_solution), rhs=rhs, w0=w0, reaction=reaction, diffusion=diffusion)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
                   backend="cpu-decomposed", ranks=ranks, extra=_residual_extra(r))
 
@@ -111,7 +117,7 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
                  overlap: bool = True, vec_b: int = 0, waves_b: int = 0, tile_rows_b: int = -1,
                  poison_halos: bool = False, b_ring: bool = False, placement: int = 0,
                  placement_budget_s: float = 0.5, placement_keep_free: float = 0.5, block_tiles: int = -1,
-                 algo: str | int = -1, ca_s: int = 3, reaction=None):
+                 algo: str | int = -1, ca_s: int = 3, reaction=None, diffusion=None):
     """Native GPU session with `ranks` subdomains on one device (LocalComm when ranks > 1).
 
     overlap: ghost exchange on a second stream concurrent with pcg_b (only matters for ranks > 1).
@@ -141,7 +147,16 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
     field (the shift field): with dtype "fp32" / "mixed" its operator is A + fp32(σ + c) everywhere.
     Session.set_reaction(c) replaces the field in place (captured graphs stay valid); step() then raises until
     the next init() / solve().  The rules of sigma != 0 apply at any sigma: pcg1 on the row march, ValueError
-    for algo="ca" / "pcg2", exact=True, block_tiles=1 and checkpoints; error_norms needs exact=."""
+    for algo="ca" / "pcg2", exact=True, block_tiles=1 and checkpoints; error_norms needs exact=.
+
+    diffusion: an (M+1)x(N+1) float64 field k(x, y) of nodal values, finite and > 0 on EVERY node (the box
+    boundary included): the session's operator is -∇·k∇ + σ + c, see solve().  The same kinds of objects as
+    reaction.  The session keeps two complete face-coefficient fields, aκ = (0.5 (k[i-1,j] + k[i,j])) a and
+    bκ = (0.5 (k[i,j-1] + k[i,j])) b, formed in fp64 and rounded ONCE to its storage type, behind the shift field
+    (which a diffusion session always holds: T(σ + c), c = 0 without reaction); its sweeps read them in place of
+    the 1-D tables.  dtype "fp32" runs the mixed arithmetic (fp32 fields, fp64 registers) on such a session.
+    Session.set_diffusion(k) replaces the fields in place, as set_reaction does; the refusals of reaction
+    apply."""
     n = _native()
     algo = {"auto": -1, "pcg1": 1, "pcg2": 2, "ca": 3}.get(algo, algo) if isinstance(algo, str) else algo
     return n.Session(problem.to_native(), world=int(ranks), comm="self" if ranks == 1 else "local",
@@ -150,7 +165,8 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
                      check=check, overlap=overlap, vec_b=vec_b, waves_b=waves_b, tile_rows_b=tile_rows_b,
                      poison_halos=poison_halos, b_ring=b_ring, placement=placement,
                      placement_budget_s=placement_budget_s, placement_keep_free=placement_keep_free,
-                     block_tiles=block_tiles, algo=int(algo), ca_s=int(ca_s), reaction=reaction)
+                     block_tiles=block_tiles, algo=int(algo), ca_s=int(ca_s), reaction=reaction,
+                     diffusion=diffusion)
 
 
 def solve_hip(problem: PoissonEllipse, ranks: int = 1, keep_solution: bool = True, poll_batches: int = 1,

@@ -80,12 +80,14 @@ def moment_gram(Y: list, D: torch.Tensor, s: int, h: float) -> torch.Tensor:
 
 
 class TorchSStepPCG:
-    def __init__(self, problem, s: int = 3, device="cpu", gram: str = "moments", reaction=None):
+    def __init__(self, problem, s: int = 3, device="cpu", gram: str = "moments", reaction=None, diffusion=None):
         self.gram = gram
         if s < 1:
             raise ValueError("s must be >= 1")
         if reaction is not None:
             raise ValueError("the s-step PCG is not built for a reaction field")
+        if diffusion is not None:
+            raise ValueError("the s-step PCG is not built for a diffusion field")
         if getattr(problem, "sigma", 0.0) != 0.0:
             raise ValueError("the s-step PCG is not built for sigma != 0")
         self.p = problem

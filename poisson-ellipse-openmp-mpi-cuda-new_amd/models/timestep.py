@@ -17,7 +17,7 @@ class BackwardEuler:
     (M+1) x (N+1) float64; g may be a scalar.  The problem's stop rule carries over: with stop="residual"
     every step solves to rtol relative to its own right-hand side u/dt + g, not to the already small
     residual of its start w0 = u.  reaction=c in session_kw (make_session's / solve()'s field, every backend)
-    steps u_t = Δu - c u + g."""
+    steps u_t = Δu - c u + g; diffusion=k likewise steps u_t = ∇·(k∇u) + g (variable conductivity)."""
 
     def __init__(self, problem: PoissonEllipse, dt: float, backend: str = "hip", **session_kw):
         if not (isinstance(dt, (int, float)) and math.isfinite(dt) and dt > 0):
@@ -57,7 +57,7 @@ class ThetaScheme:
     a NumPy array out.  Every other backend of solve() takes and returns NumPy arrays.  All fields are
     (M+1) x (N+1) float64.  `last` holds the statistics of the last step's solve, and the problem's stop rule
     carries over as in BackwardEuler.  reaction=c in session_kw adds the field to L, on both sides of the step:
-    the solve and the apply of the right-hand side."""
+    the solve and the apply of the right-hand side; diffusion=k likewise makes A the k operator on both sides."""
 
     def __init__(self, problem: PoissonEllipse, dt: float, theta: float = 0.5, backend: str = "hip", **session_kw):
         if not (isinstance(dt, (int, float)) and math.isfinite(dt) and dt > 0):
@@ -86,7 +86,7 @@ class ThetaScheme:
         on_device = hasattr(u, "__cuda_array_interface__")
         if on_device and self.session is not None:
             return self.session.apply(u, **kw)  # the session's operator: its reaction field included
-        return self.problem.apply(u, reaction=self.kw.get("reaction"), **kw)
+        return self.problem.apply(u, reaction=self.kw.get("reaction"), diffusion=self.kw.get("diffusion"), **kw)
 
     def step(self, u, g=None):
         rhs = self.rhs(u, g)

@@ -19,16 +19,20 @@ from .solvers import Result
 
 
 class TorchPCG:
-    def __init__(self, problem, device="cpu", dtype=torch.float64, comm=None, split="reference", reaction=None):
+    def __init__(self, problem, device="cpu", dtype=torch.float64, comm=None, split="reference", reaction=None,
+                 diffusion=None):
         """reaction: optional global (M+1)x(N+1) float64 field c >= 0 (NumPy or a CPU tensor; boundary values
-        ignored): the operator is A + (sigma + c) I, the diagonal D + sigma + c."""
+        ignored): the operator is A + (sigma + c) I, the diagonal D + sigma + c.
+        diffusion: optional global (M+1)x(N+1) float64 field k > 0 on every node: the face coefficients are
+        multiplied by the mean of k over the two nodes of the face (ops.reference.assemble)."""
         self.p = problem
         self.comm = comm or SingleComm()
         self.device = torch.device(device)
         self.dtype = dtype
         Px, Py = process_grid(self.comm.world, problem.M, problem.N, split)
         self.sd = subdomain(problem.M, problem.N, Px, Py, self.comm.rank)
-        self.a, self.b, self.B = R.assemble(problem, self.sd, self.device, dtype)
+        self.a, self.b, self.B = R.assemble(problem, self.sd, self.device, dtype,
+                                            diffusion=problem.diffusion_field(diffusion))
         self.nbs = neighbours(self.sd)
         self.shift = problem.sigma  # a number, or with a reaction field the (nx, ny) tensor sigma + c
         c = problem.reaction_field(reaction)

@@ -12,7 +12,10 @@ from ..utils.native import load as _native
 
 
 class DeviceOps:
-    def __init__(self, problem, Px: int = 1, Py: int = 1, rank: int = 0, device: int = 0, reaction=None):
+    def __init__(self, problem, Px: int = 1, Py: int = 1, rank: int = 0, device: int = 0, reaction=None, diffusion=None):
+        if diffusion is not None:
+            raise ValueError("DeviceOps evaluates -div(grad u) with k = 1 alone: not built for a diffusion field (use a "
+                             "native session: solve(problem, 'hip', diffusion=k) / make_session(problem, diffusion=k))")
         if reaction is not None:
             raise ValueError("DeviceOps evaluates -div(k grad u) alone: not built for a reaction field (use a native "
                              "session: solve(problem, 'hip', reaction=c) / make_session(problem, reaction=c))")

@@ -58,8 +58,11 @@ def inside(problem, sd, device="cpu"):
     return (x / problem.ax) ** 2 + (y / problem.by) ** 2 < 1.0
 
 
-def assemble(problem, sd, device="cpu", dtype=torch.float64):
-    """a, b over the local array incl. ghosts, B (RHS) on the interior.  Shapes (nx+2, ny+2)."""
+def assemble(problem, sd, device="cpu", dtype=torch.float64, diffusion=None):
+    """a, b over the local array incl. ghosts, B (RHS) on the interior.  Shapes (nx+2, ny+2).
+    diffusion: optional global (M+1)x(N+1) float64 field k > 0 of nodal values: a[i,j] <- (0.5 (k[i-1,j] +
+    k[i,j])) a[i,j], b[i,j] <- (0.5 (k[i,j-1] + k[i,j])) b[i,j] in fp64, on the faces between two nodes of the
+    box."""
     T = face_tables(problem, device)
     gi, gj = local_index(sd)
     gi, gj = gi.to(device), gj.to(device)
@@ -67,6 +70,11 @@ def assemble(problem, sd, device="cpu", dtype=torch.float64):
     xlo, xhi, rh = T["xlo"][gi][:, None], T["xhi"][gi][:, None], T["rh"][gj][None, :]
     a = _face_coef(_clip_len(ylo, yhi, rv), problem.h2, problem.eps)
     b = _face_coef(_clip_len(xlo, xhi, rh), problem.h1, problem.eps)
+    if diffusion is not None:
+        k = torch.as_tensor(diffusion, dtype=torch.float64).to(device)
+        kc = k[gi][:, gj]
+        a = torch.where((gi >= 1)[:, None], (0.5 * (k[(gi - 1).clamp(min=0)][:, gj] + kc)) * a, a)
+        b = torch.where((gj >= 1)[None, :], (0.5 * (k[gi][:, (gj - 1).clamp(min=0)] + kc)) * b, b)
     mask = inside(problem, sd, device)
     B = torch.where(mask, torch.full_like(a, problem.F), torch.zeros_like(a))
     B[0, :] = 0
