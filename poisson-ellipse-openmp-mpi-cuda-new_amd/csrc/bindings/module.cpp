@@ -39,10 +39,11 @@ struct FieldArg {
   py::array_t<double, py::array::c_style> arr;  // owns (or shares) the data `ptr` points to
   const double* ptr = nullptr;
 };
-// reaction: a reaction field instead -- the same type, dtype and shape rules; finite and >= 0 on the interior
-// nodes, its box-boundary values ignored and not read.  kind 2: a diffusion field -- finite and > 0 on EVERY node.
-FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::string& name, int kind = 0) {
-  const bool reaction = kind == 1;
+// rule: the values a field of this role may hold (pmx/operator.hpp) -- rhs and w0 finite; a reaction field finite
+// and >= 0 on the interior nodes, its box-boundary values ignored and not read; a diffusion field finite and > 0
+// on EVERY node.  The same type, dtype and shape rules for all.
+FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::string& name,
+                   FieldRule rule = FieldRule::kFinite) {
   FieldArg f;
   if (obj.is_none()) return f;
   py::object a = obj;
@@ -61,20 +62,7 @@ FieldArg field_arg(const py::object& obj, const ProblemSpec& s, const std::strin
   f.arr = py::array_t<double, py::array::c_style>::ensure(arr);
   if (!f.arr) throw py::value_error(name + ": cannot be read as a C-contiguous float64 array");
   const double* d = f.arr.data();
-  if (reaction) {
-    for (int i = 1; i <= s.M - 1; ++i)
-      for (int j = 1; j <= s.N - 1; ++j) {
-        const double v = d[py::ssize_t(i) * (s.N + 1) + j];
-        if (!(std::isfinite(v) && v >= 0.0))
-          throw py::value_error(name + " must be finite and >= 0 on every interior node");
-      }
-  } else if (kind == 2) {
-    for (py::ssize_t k = 0; k < f.arr.size(); ++k)
-      if (!(std::isfinite(d[k]) && d[k] > 0.0)) throw py::value_error(name + " must be finite and > 0 on every node");
-  } else {
-    for (py::ssize_t k = 0; k < f.arr.size(); ++k)
-      if (!std::isfinite(d[k])) throw py::value_error(name + " holds non-finite values");
-  }
+  if (!field_values_ok(d, s.N + 1, s.M, s.N, rule)) throw py::value_error(name + field_rule_text(rule));
   f.ptr = d;
   return f;
 }
@@ -139,18 +127,28 @@ struct SessionField {
   UserField f;
 };
 SessionField session_field(const py::object& obj, const ProblemSpec& sp, int device, const std::string& name,
-                           int kind = 0) {
+                           FieldRule rule = FieldRule::kFinite) {
   SessionField r;
   if (!obj.is_none() && py::hasattr(obj, "__cuda_array_interface__")) {
     r.f = device_field(obj, sp, device, name);
   } else {
-    r.host = field_arg(obj, sp, name, kind);
+    r.host = field_arg(obj, sp, name, rule);
     r.f = UserField(r.host.ptr);
   }
   return r;
 }
 SessionField session_field(const py::object& obj, Session& s, const std::string& name) {
   return session_field(obj, s.solver(0).spec(), s.solver(0).device(), name);
+}
+// Session.set_reaction / set_diffusion: the field under its role's rules, then the session's own checks
+void replace_field(Session& s, const py::object& obj, bool diffusion) {
+  const std::string name = diffusion ? "diffusion" : "reaction";
+  if (obj.is_none()) throw py::value_error(name + " must be an (M+1) x (N+1) float64 field");
+  const SessionField f = session_field(obj, s.solver(0).spec(), s.solver(0).device(), name,
+                                       diffusion ? FieldRule::kPositive : FieldRule::kNonNegInterior);
+  py::gil_scoped_release g;
+  if (diffusion) s.set_diffusion(f.f);
+  else s.set_reaction(f.f);
 }
 
 // The Python-orchestrated paths (OpContext ops, SubdomainSolver + comm_layout under DistGpuPCG
@@ -435,7 +433,8 @@ PYBIND11_MODULE(_pmx, m) {
                         py::object reaction, py::object diffusion) {
           s.validate();
           const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
-          const FieldArg c = field_arg(reaction, s, "reaction", 1), kf = field_arg(diffusion, s, "diffusion", 2);
+          const FieldArg c = field_arg(reaction, s, "reaction", FieldRule::kNonNegInterior),
+                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive);
           SolveResult r;
           { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep, f.ptr, w.ptr, c.ptr, kf.ptr); }
           return result_dict(r, s, keep);
@@ -446,7 +445,8 @@ PYBIND11_MODULE(_pmx, m) {
                                    py::object rhs, py::object w0, py::object reaction, py::object diffusion) {
           s.validate();
           const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
-          const FieldArg c = field_arg(reaction, s, "reaction", 1), kf = field_arg(diffusion, s, "diffusion", 2);
+          const FieldArg c = field_arg(reaction, s, "reaction", FieldRule::kNonNegInterior),
+                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive);
           SolveResult r;
           {
             py::gil_scoped_release nogil;
@@ -461,7 +461,8 @@ PYBIND11_MODULE(_pmx, m) {
   m.def("cpu_apply", [](const ProblemSpec& s, py::array_t<double, py::array::c_style> x, py::object y, double alpha,
                         double beta, double gamma, double c0, py::object reaction, py::object diffusion) {
           s.validate();
-          const FieldArg c = field_arg(reaction, s, "reaction", 1), kf = field_arg(diffusion, s, "diffusion", 2);
+          const FieldArg c = field_arg(reaction, s, "reaction", FieldRule::kNonNegInterior),
+                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive);
           auto fits = [&](const py::array& a) { return a.ndim() == 2 && a.shape(0) == s.M + 1 && a.shape(1) == s.N + 1; };
           py::array_t<double, py::array::c_style> ya;
           if (!y.is_none()) ya = y.cast<py::array_t<double, py::array::c_style>>();
@@ -695,16 +696,11 @@ PYBIND11_MODULE(_pmx, m) {
              s.validate();
              // type, dtype, shape, stride and device of the field (and a host field's values) before anything
              // else; the Session checks a device field's values, still before it allocates
-             const SessionField rf = session_field(reaction, s, devices.empty() ? device : devices[0], "reaction", true);
-             c.reaction = rf.f.ptr;
-             c.reaction_ld = rf.f.ld;
-             c.reaction_on_device = rf.f.on_device;
-             c.reaction_stream = rf.f.stream;
-             const SessionField df = session_field(diffusion, s, devices.empty() ? device : devices[0], "diffusion", 2);
-             c.diffusion = df.f.ptr;
-             c.diffusion_ld = df.f.ld;
-             c.diffusion_on_device = df.f.on_device;
-             c.diffusion_stream = df.f.stream;
+             const int dev0 = devices.empty() ? device : devices[0];
+             const SessionField rf = session_field(reaction, s, dev0, "reaction", FieldRule::kNonNegInterior);
+             const SessionField df = session_field(diffusion, s, dev0, "diffusion", FieldRule::kPositive);
+             c.reaction = rf.f;
+             c.diffusion = df.f;
              c.sharing = sharing;
              c.spec = s;
              c.opt = make_options(device, kernel, block, vec, waves, tile_rows, dtype, exact,
@@ -742,23 +738,15 @@ PYBIND11_MODULE(_pmx, m) {
            py::arg("placement_keep_free") = 0.5, py::arg("sharing") = 0, py::arg("block_tiles") = -1,
            py::arg("ca_s") = 3, py::arg("split_sweep") = -1, py::arg("reaction") = py::none(),
            py::arg("diffusion") = py::none())
-      .def("set_diffusion", [](Session& s, py::object diffusion) {
-             if (diffusion.is_none()) throw py::value_error("diffusion must be an (M+1) x (N+1) float64 field");
-             const SessionField df = session_field(diffusion, s.solver(0).spec(), s.solver(0).device(), "diffusion", 2);
-             py::gil_scoped_release g;
-             s.set_diffusion(df.f);
-           }, py::arg("diffusion"),
+      .def("set_diffusion", [](Session& s, py::object diffusion) { replace_field(s, diffusion, true); },
+           py::arg("diffusion"),
            "replace the diffusion field k of a session built with one (make_session(p, diffusion=k)): the same "
            "types and checks as there (a NumPy array, a CPU tensor or a float64 device array; finite and > 0 on "
            "EVERY node, ValueError before the session is touched).  The face-coefficient fields are rewritten in "
            "place, so captured graphs stay valid; step() raises until the next init() / solve()")
       .def_property_readonly("has_diffusion", &Session::has_diffusion)
-      .def("set_reaction", [](Session& s, py::object reaction) {
-             if (reaction.is_none()) throw py::value_error("reaction must be an (M+1) x (N+1) float64 field");
-             const SessionField rf = session_field(reaction, s.solver(0).spec(), s.solver(0).device(), "reaction", true);
-             py::gil_scoped_release g;
-             s.set_reaction(rf.f);
-           }, py::arg("reaction"),
+      .def("set_reaction", [](Session& s, py::object reaction) { replace_field(s, reaction, false); },
+           py::arg("reaction"),
            "replace the reaction field c of a session built with one (make_session(p, reaction=c)): the same "
            "types and checks as there (a NumPy array, a CPU tensor or a float64 device array; finite and >= 0 on "
            "the interior nodes, ValueError before the session is touched).  The shift field is rewritten in place, "

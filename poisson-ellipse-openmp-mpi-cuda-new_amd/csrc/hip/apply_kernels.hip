@@ -32,6 +32,7 @@
 // the next row (carried over like the table value), bk of the node and of the column after it.
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "pcg_device.hpp"
 #include "pmx/common.hpp"
@@ -181,29 +182,21 @@ void launch_apply(const DevGeom& G, const DevTables& Tb, const double* x, int64_
   const int64_t gy = (int64_t(rows) + kApplyRows - 1) / kApplyRows;
   PMX_CHECK(gy <= 65535, "too many rows for one launch: " << rows);
   const dim3 grid(unsigned((cols + kApplyCols - 1) / kApplyCols), unsigned(gy)), block(kApplyCols);
-  const bool sh = K.sigma != 0.0;
-#define PMX_APPLY(...) \
-  hipLaunchKernelGGL((k_apply<__VA_ARGS__>), grid, block, 0, s, G, Tb, x, ldx, y, ldy, out, ldo, gi_lo, gj_lo, rows, cols, K)
-  if (K.ka) {
-    PMX_CHECK(K.shift && K.kb && (K.selem == 8 || K.selem == 4), "k_apply: a diffusion session holds the shift field "
-                                                                  "and both face fields, fp64 or fp32");
-    if (K.selem == 8 && y) PMX_APPLY(3, true, double);
-    else if (K.selem == 8) PMX_APPLY(3, false, double);
-    else if (y) PMX_APPLY(3, true, float);
-    else PMX_APPLY(3, false, float);
-  }
-  else if (K.shift) {
-    PMX_CHECK(K.selem == 8 || K.selem == 4, "k_apply: the shift field is fp64 or fp32");
-    if (K.selem == 8 && y) PMX_APPLY(2, true, double);
-    else if (K.selem == 8) PMX_APPLY(2, false, double);
-    else if (y) PMX_APPLY(2, true, float);
-    else PMX_APPLY(2, false, float);
-  }
-  else if (sh && y) PMX_APPLY(1, true);
-  else if (sh) PMX_APPLY(1, false);
-  else if (y) PMX_APPLY(0, true);
-  else PMX_APPLY(0, false);
-#undef PMX_APPLY
+  PMX_CHECK(!K.shift || K.selem == 8 || K.selem == 4, "k_apply: the shift and face fields are fp64 or fp32");
+  // k_apply<SH, HAS_Y, T>: T is the storage type of the fields, double for the kinds that read none
+  with_op_kind(OperatorData<void>{K.sigma, K.shift, K.ka, K.kb}.kind(), [&](auto sh) {
+    constexpr int SH = int(decltype(sh)::value);
+    auto launch = [&](auto t, auto has_y) {
+      hipLaunchKernelGGL((k_apply<SH, decltype(has_y)::value, decltype(t)>), grid, block, 0, s, G, Tb, x, ldx, y, ldy, out,
+                         ldo, gi_lo, gj_lo, rows, cols, K);
+    };
+    auto with_y = [&](auto t) { y ? launch(t, std::true_type{}) : launch(t, std::false_type{}); };
+    if constexpr (SH >= 2) {
+      if (K.selem == 8) return with_y(double{});
+      return with_y(float{});
+    }
+    with_y(double{});
+  });
   HIP_CHECK(hipGetLastError());
 }
 

@@ -214,11 +214,11 @@ GpuOptions resolve_options(const GpuOptions& in) {
 
 void apply_sigma_rules(const ProblemSpec& spec, const ProcGrid& grid, GpuOptions& o) {
   PMX_CHECK(o.resolved, "apply_sigma_rules needs resolve_options()");
-  if (spec.sigma == 0.0 && !o.reaction) return;
+  if (spec.sigma == 0.0 && !o.shift_field) return;
   auto refuse = [&](const char* option) {
-    throw std::invalid_argument(std::string(o.diffusion  ? "a diffusion field"
-                                            : o.reaction ? "a reaction field"
-                                                         : "sigma != 0 (the screened problem)") +
+    throw std::invalid_argument(std::string(o.diffusion     ? "a diffusion field"
+                                            : o.shift_field ? "a reaction field"
+                                                            : "sigma != 0 (the screened problem)") +
                                 " runs pcg1 on the row march only: " + option + " is not built for it");
   };
   if (o.algo == 3) refuse("algo=\"ca\" (the s-step PCG)");
@@ -339,8 +339,8 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
   const int gh = ca_ && sd.grid.size() > 1 ? (ca_fuse_ ? 2 * opt_.ca_s : opt_.ca_s) : 2;
   PMX_CHECK(!pcg1_ || (!opt.exact && (sd.grid.size() == 1 || (sd.nx >= 2 && sd.ny >= 2))),
             "pcg1 needs the fast arithmetic and a subdomain of at least 2 x 2 nodes");
-  PMX_CHECK(!opt_.diffusion || (pcg1_ && opt_.reaction), "a diffusion field runs pcg1 with the shift field");
-  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh, opt_.reaction != 0, opt_.diffusion != 0);
+  PMX_CHECK(!opt_.diffusion || (pcg1_ && opt_.shift_field), "a diffusion field runs pcg1 with the shift field");
+  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh, opt_.shift_field != 0, opt_.diffusion != 0);
   const int elem = int(plan_.elem);
   geom_ = make_dev_geom(spec, sd, plan_.pitch);
   const DevGeom& G = geom_;
@@ -688,7 +688,7 @@ void GpuSubdomainSolver::set_init_data(const double* f, const double* w0, int64_
 }
 
 void GpuSubdomainSolver::set_reaction(const double* c, int64_t ld, bool on_device, hipStream_t s) {
-  PMX_CHECK(has_reaction(), "set_reaction needs a solver built with a reaction field (GpuOptions::reaction)");
+  PMX_CHECK(has_shift_field(), "set_reaction needs a solver built with a shift field (GpuOptions::shift_field)");
   PMX_CHECK(c && ld >= spec_.N + 1, "set_reaction needs an (M+1) x (N+1) array with row stride >= N+1");
   HIP_CHECK(hipSetDevice(opt_.device));
   // the block with its radius-2 frame (local rows -1 .. nx+2, columns -1 .. ny+2), clipped to the interior
@@ -779,10 +779,7 @@ double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_
     X.ca = pw.a[0];
     X.cb = pw.a[1];
     X.npend = pw.n;
-    X.sigma = spec_.sigma;
-    X.shift = shift<T>();
-    X.ka = face<T>(0);
-    X.kb = face<T>(1);
+    set_operator(X, op<T>());
     launch_init_data<T>(geom_, tables_, fields<T>().w, nullptr, HaloBufs<T>{}, part, init_tiles_, X, true, s);
   });
   HIP_CHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -895,7 +892,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
   // recovered p^{k-2} carries the STORAGE rounding of p^{k-1} and r^{k-1} times 1 / beta_{k-1}: with fp32
   // fields w then misses the oracle by 2.7e-6 max|w| where re-reading p^{k-2} gives 7e-8 (measured, 40x40
   // and 97x130, constant rhs).  There the sweep re-reads below beta = 0.5 (growth <= 3 roundings).
-  if ((spec_.sigma != 0.0 || has_reaction()) && sizeof(T) == 4 && opt_.pair_w != 2) st.pair_min_beta = 0.5;
+  if ((spec_.sigma != 0.0 || has_shift_field()) && sizeof(T) == 4 && opt_.pair_w != 2) st.pair_min_beta = 0.5;
   st.w_cycle = w_cycle();
   // stop rule: the step rule leaves PcgState's tail zero, as every build before it did
   stop_ref_data_ = false;
@@ -925,10 +922,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     X.fpitch = geom_.pitch;
     X.has_f = !stage_f_.empty() || dev_f_;
     X.has_w = !stage_w_.empty() || dev_w_;
-    X.sigma = spec_.sigma;
-    X.shift = shift<T>();
-    X.ka = face<T>(0);
-    X.kb = face<T>(1);
+    set_operator(X, op<T>());
     X.rho_b = stop_ref_data_ ? 1 : 0;
     // the same cells from either source: a staged host copy, or the caller's device block through the
     // scatter kernel (set_init_data_device)
@@ -955,8 +949,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     std::vector<char>().swap(stage_w_);
     dev_f_ = dev_w_ = nullptr;
   } else {
-    launch_init<T>(G, tables_, w, r, halo<T>(), partials_.get(), init_tiles_, s, spec_.sigma, shift<T>(), face<T>(0),
-                   face<T>(1));
+    launch_init<T>(G, tables_, w, r, halo<T>(), partials_.get(), init_tiles_, s, op<T>());
     after_launch(s);
   }
   // red_b[1] = (z^0, r^0); red_b[0] = rho_B = (D^-1 B, B) when the residual rule starts from a w0, else 0
@@ -1047,7 +1040,7 @@ void GpuSubdomainSolver::kernel_a(hipStream_t s, int part) {
   }
   if (pcg1_)
     launch_pcg1<T>(geom_, tables_, F.w, F.r, F.r2, F.p0, F.p1, partials_.get(), state_, tiles1_for(w_sweep_next()), s,
-                   part, w_sweep_next(), spec_.sigma, shift<T>(), face<T>(0), face<T>(1));
+                   part, w_sweep_next(), op<T>());
   else
     launch_pcg_a_wave<T>(geom_, tables_, F.r, F.p0, F.p1, halo<T>(), partials_.get(), state_, tiles_, opt_.exact, s);
 }

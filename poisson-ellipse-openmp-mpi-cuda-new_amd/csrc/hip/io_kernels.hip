@@ -188,13 +188,12 @@ void launch_scatter_shift(const double* src, int64_t ld, T* dst, int64_t pitch, 
 template void launch_scatter_shift<double>(const double*, int64_t, double*, int64_t, int, int, double, hipStream_t);
 template void launch_scatter_shift<float>(const double*, int64_t, float*, int64_t, int, int, double, hipStream_t);
 
-void launch_reaction_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s) {
-  hipLaunchKernelGGL(k_reaction_check, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);
-  HIP_CHECK(hipGetLastError());
-}
-
-void launch_diffusion_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s) {
-  hipLaunchKernelGGL(k_diffusion_check, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);
+void launch_value_check(FieldRule rule, const double* field, int64_t ld, int M, int N, int* flag, hipStream_t s) {
+  const bool inner = rule == FieldRule::kNonNegInterior;  // the interior nodes only
+  const double* src = inner ? field + ld + 1 : field;
+  const int rows = inner ? M - 1 : M + 1, cols = inner ? N - 1 : N + 1;
+  const auto k = rule == FieldRule::kFinite ? k_finite : inner ? k_reaction_check : k_diffusion_check;
+  hipLaunchKernelGGL(k, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -210,11 +209,6 @@ template void launch_face_fields<double>(const DevGeom&, const DevTables&, const
                                          hipStream_t);
 template void launch_face_fields<float>(const DevGeom&, const DevTables&, const double*, int64_t, float*, float*,
                                         hipStream_t);
-
-void launch_finite_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s) {
-  hipLaunchKernelGGL(k_finite, io_grid(rows, cols), dim3(kIoCols), 0, s, src, ld, rows, cols, flag);
-  HIP_CHECK(hipGetLastError());
-}
 
 template <typename T>
 void launch_gather(const T* w, const T* pa, double ca, const T* pb, double cb, int npend, int64_t pitch,

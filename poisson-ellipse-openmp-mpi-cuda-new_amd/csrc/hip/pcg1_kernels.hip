@@ -615,10 +615,20 @@ int pcg1_lds_pad(int wpcu, int waves) {
   return std::max(0, per_wg - waves * 4096);
 }
 
+// The k_pcg1 launch, spelled here and nowhere else: the sweep that moves w (wsweep) or its twin, for the operator
+// kind K (OpKind -> the kernel's SH, DIF: pcg1_sh, pcg1_dif); args: the kernel's arguments
+template <typename T, typename C, int V, int WV, int PF, int DPF, OpKind K, typename... Args>
+void run_pcg1(bool wsweep, int nb, int bs, int lds, hipStream_t s, const Args&... args) {
+  if (wsweep)
+    hipLaunchKernelGGL((k_pcg1<T, C, V, WV, PF, true, DPF, pcg1_sh(K), pcg1_dif(K)>), dim3(nb), dim3(bs), lds, s, args...);
+  else
+    hipLaunchKernelGGL((k_pcg1<T, C, V, WV, PF, false, DPF, pcg1_sh(K), pcg1_dif(K)>), dim3(nb), dim3(bs), lds, s, args...);
+}
+
 template <typename T>
 void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0, T* p1,
                  double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part, bool wsweep,
-                 double sigma, const T* shift, const T* ka, const T* kb) {
+                 const OperatorData<T>& op) {
   PMX_CHECK(tc.kind == 3, "launch_pcg1 needs make_pcg1_tiles");
   PMX_CHECK(part >= 0 && part <= 2, "launch_pcg1: part must be 0, 1 or 2");
   const int tiles = part == 0 ? tc.ntiles() : part == 1 ? tc.interior_tiles() : tc.ntiles() - tc.interior_tiles();
@@ -628,89 +638,53 @@ void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0
   PMX_CHECK(tc.waves == 1 || grouped, "pcg1: workgroups of several waves need the grouped dispatch order");
   const int nb = grouped ? tc.groups[part] : tiles;
   const int count = grouped ? nb * tc.waves : tiles;
-  const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, ord, count, sigma, shift, ka, kb};
+  const Pcg1Part P{part, tc.tiles_i, tc.ti_lo, tc.ti_hi, tc.tj_lo, tc.tj_hi, ord, count, op.sigma, op.shift, op.ka, op.kb};
   if (tiles == 0) return;
   PMX_CHECK(G.nb == 0 || (G.nx >= 2 && G.ny >= 2), "pcg1 on a decomposed grid needs subdomains >= 2 x 2");
   const int bs = 64 * tc.waves;
-#define PMX_PCG1_CD(C, V, WV, PF, D)                                                                     \
-  do {                                                                                                   \
-    if (wsweep)                                                                                          \
-      hipLaunchKernelGGL((k_pcg1<T, C, V, WV, PF, true, D>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, r2, \
-                         p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);                      \
-    else                                                                                                 \
-      hipLaunchKernelGGL((k_pcg1<T, C, V, WV, PF, false, D>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, r2, \
-                         p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);                      \
-  } while (0)
+#define PMX_PCG1_RUN(C, V, WV, PF, D, K)                                                                 \
+  run_pcg1<T, C, V, WV, PF, D, K>(wsweep, nb, bs, tc.lds_pad, s, G, Tb, w, r, r2, p0, p1, partials, S, tc.rows, \
+                                  tc.tiles_j, tc.ntiles(), P)
+  // the sweeps of the screened problem, of a session with a reaction field (its shift field holds sigma + c, so
+  // sigma itself is not read) and of one with a diffusion field: the shapes the library picks on its own -- VEC 2,
+  // 1 wave, register prefetch 1 or 2; the diffusion sweeps in fp64 registers for either storage type (dtype
+  // "fp32" runs the mixed arithmetic)
+  const OpKind kind = op.kind();
+  if (kind != OpKind::kPlain) {
+    const bool shape = tc.vec == 2 && tc.waves == 1 && (tc.pf == 1 || tc.pf == 2) && tc.dpf == 0;
+    if (kind == OpKind::kDiffusion)
+      PMX_CHECK(shape && !tc.arith32,
+                "pcg1 with a diffusion field runs the default tile shapes (vec 2 x 1 wave, prefetch 1 or 2, no "
+                "LDS-DMA) in fp64 registers");
+    PMX_CHECK(shape, "pcg1 with sigma != 0 or a reaction field runs the default tile shapes (vec 2 x 1 wave, prefetch 1 "
+                     "or 2, no LDS-DMA)");
+    PMX_CHECK(!tc.arith32 || sizeof(T) == 4, "pcg1: fp32 arithmetic needs fp32 storage");
+    with_op_kind(kind, [&](auto k) {
+      constexpr OpKind K = decltype(k)::value;
+      if constexpr (K != OpKind::kPlain) {
+        auto run = [&](auto c) {
+          if (tc.pf == 1) PMX_PCG1_RUN(decltype(c), 2, 1, 1, 0, K);
+          else PMX_PCG1_RUN(decltype(c), 2, 1, 2, 0, K);
+        };
+        if constexpr (std::is_same_v<T, float> && K != OpKind::kDiffusion) {
+          if (tc.arith32) return run(float{});
+        }
+        run(double{});
+      }
+    });
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   // the LDS-DMA march (tc.dpf rows ahead): fp64 storage and arithmetic, the default tile shape
 #define PMX_PCG1_C(C, V, WV, PF)                                                                         \
   do {                                                                                                   \
     if constexpr (sizeof(T) == 8 && std::is_same_v<C, double> && V == 2 && WV == 1 && PF == 1) {        \
-      if (tc.dpf == 2) { PMX_PCG1_CD(C, V, WV, PF, 2); break; }                                          \
-      if (tc.dpf == 3) { PMX_PCG1_CD(C, V, WV, PF, 3); break; }                                          \
+      if (tc.dpf == 2) { PMX_PCG1_RUN(C, V, WV, PF, 2, OpKind::kPlain); break; }                         \
+      if (tc.dpf == 3) { PMX_PCG1_RUN(C, V, WV, PF, 3, OpKind::kPlain); break; }                         \
     }                                                                                                    \
     PMX_CHECK(tc.dpf == 0, "pcg1: the LDS-DMA march needs fp64, VEC 2 x 1 wave, prefetch 1 and dpf 2 or 3"); \
-    PMX_PCG1_CD(C, V, WV, PF, 0);                                                                        \
+    PMX_PCG1_RUN(C, V, WV, PF, 0, OpKind::kPlain);                                                       \
   } while (0)
-  // the screened problem's sweeps (SH): the shapes the library picks on its own -- VEC 2, 1 wave,
-  // register prefetch 1 or 2.  MODE: kShiftSigma, or kShiftField for a session with a reaction field
-  // (its shift field holds sigma + c, so sigma itself is not read)
-#define PMX_PCG1_SH(C, PF, MODE)                                                                         \
-  do {                                                                                                   \
-    if (wsweep)                                                                                          \
-      hipLaunchKernelGGL((k_pcg1<T, C, 2, 1, PF, true, 0, MODE>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, \
-                         r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);                  \
-    else                                                                                                 \
-      hipLaunchKernelGGL((k_pcg1<T, C, 2, 1, PF, false, 0, MODE>), dim3(nb), dim3(bs), tc.lds_pad, s, G, Tb, w, r, \
-                         r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);                  \
-  } while (0)
-#define PMX_PCG1_SHIFT(MODE)                                                                             \
-  do {                                                                                                   \
-    if (f32) {                                                                                           \
-      if constexpr (std::is_same_v<T, float>) {                                                          \
-        if (tc.pf == 1) PMX_PCG1_SH(float, 1, MODE);                                                     \
-        else PMX_PCG1_SH(float, 2, MODE);                                                                \
-      }                                                                                                  \
-    } else if (tc.pf == 1) {                                                                             \
-      PMX_PCG1_SH(double, 1, MODE);                                                                      \
-    } else {                                                                                             \
-      PMX_PCG1_SH(double, 2, MODE);                                                                      \
-    }                                                                                                    \
-  } while (0)
-  // the diffusion sweeps: fp64 registers for either storage type (dtype "fp32" runs the mixed arithmetic)
-#define PMX_PCG1_DIF(PF)                                                                                 \
-  do {                                                                                                   \
-    if (wsweep)                                                                                          \
-      hipLaunchKernelGGL((k_pcg1<T, double, 2, 1, PF, true, 0, kShiftField, true>), dim3(nb), dim3(bs), tc.lds_pad, s, \
-                         G, Tb, w, r, r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);     \
-    else                                                                                                 \
-      hipLaunchKernelGGL((k_pcg1<T, double, 2, 1, PF, false, 0, kShiftField, true>), dim3(nb), dim3(bs), tc.lds_pad, s, \
-                         G, Tb, w, r, r2, p0, p1, partials, S, tc.rows, tc.tiles_j, tc.ntiles(), P);     \
-  } while (0)
-  if (ka) {
-    PMX_CHECK(shift && kb, "pcg1: a diffusion session holds the shift field and both face fields");
-    PMX_CHECK(tc.vec == 2 && tc.waves == 1 && (tc.pf == 1 || tc.pf == 2) && tc.dpf == 0 && !tc.arith32,
-              "pcg1 with a diffusion field runs the default tile shapes (vec 2 x 1 wave, prefetch 1 or 2, no "
-              "LDS-DMA) in fp64 registers");
-    if (tc.pf == 1) PMX_PCG1_DIF(1);
-    else PMX_PCG1_DIF(2);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-#undef PMX_PCG1_DIF
-  if (sigma != 0.0 || shift) {
-    PMX_CHECK(tc.vec == 2 && tc.waves == 1 && (tc.pf == 1 || tc.pf == 2) && tc.dpf == 0,
-              "pcg1 with sigma != 0 or a reaction field runs the default tile shapes (vec 2 x 1 wave, prefetch 1 "
-              "or 2, no LDS-DMA)");
-    bool f32 = false;
-    if constexpr (std::is_same_v<T, float>) f32 = tc.arith32 != 0;
-    PMX_CHECK(!tc.arith32 || f32, "pcg1: fp32 arithmetic needs fp32 storage");
-    if (shift) PMX_PCG1_SHIFT(kShiftField);
-    else PMX_PCG1_SHIFT(kShiftSigma);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-#undef PMX_PCG1_SHIFT
-#undef PMX_PCG1_SH
   // fp32 arithmetic: fp32 storage only, the default tile shape (VEC 2, 1 wave) and prefetch 1-3
 #define PMX_PCG1(V, WV, PF)                                                                              \
   do {                                                                                                   \
@@ -738,7 +712,7 @@ void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0
 #endif
 #undef PMX_PCG1
 #undef PMX_PCG1_C
-#undef PMX_PCG1_CD
+#undef PMX_PCG1_RUN
   HIP_CHECK(hipGetLastError());
 }
 
@@ -782,14 +756,14 @@ void* pcg1_wave_trace_setup(long long it, int nwaves) {
 #endif
 
 template void launch_pcg1<double>(const DevGeom&, const DevTables&, double*, double*, double*, double*,
-                                  double*, double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double,
-                                  const double*, const double*, const double*);
+                                  double*, double*, PcgState*, const TileCfg&, hipStream_t, int, bool,
+                                  const OperatorData<double>&);
 template void launch_pcg1_halo<double>(const DevGeom&, double*, double*, double*, double*, HaloBufs<double>,
                                         long long, bool, hipStream_t, long long*);
 template void launch_pcg1_halo<float>(const DevGeom&, float*, float*, float*, float*, HaloBufs<float>,
                                        long long, bool, hipStream_t, long long*);
 template void launch_pcg1<float>(const DevGeom&, const DevTables&, float*, float*, float*, float*, float*,
-                                 double*, PcgState*, const TileCfg&, hipStream_t, int, bool, double, const float*,
-                                 const float*, const float*);
+                                 double*, PcgState*, const TileCfg&, hipStream_t, int, bool,
+                                 const OperatorData<float>&);
 
 }  // namespace pmx

@@ -54,7 +54,8 @@ TileCfg make_tiles(const DevGeom& G, int block, int rows) {
 // Each thread keeps the w rows i-1, i, i+1 of its column in registers and takes the j-1 / j+1
 // neighbours by plain loads.
 // SH: the screened problem (ProblemSpec::sigma != 0): A w + sigma w in the residual, D + sigma in the
-// (z0, r0) partial, in every mode; sigma is InitData's last member, and the launchers pick SH from it.
+// (z0, r0) partial, in every mode; sigma is among InitData's last members, and the launchers pick SH from them
+// (OperatorData::kind; SH is the value of its OpKind).
 // SH = 2 (a session with a reaction field): the node's own shift T(sigma + c) from X.shift -- the
 // subdomain's shift field, r's layout -- in place of X.sigma, in the same two places and in rho_B.
 // SH = 3 (a session with a diffusion field): as 2, and the four faces of the node come from the session's
@@ -294,36 +295,17 @@ __global__ void k_local_allreduce(double* const* bufs, int nranks, int nq) {
     default: PMX_CHECK(false, "unsupported block " << block);           \
   }
 
+// k_init<T, B, MODE, SH> on the init tiling; K: with_op_kind's constant, its value is SH
+#define PMX_K_INIT(B, MODE, K)                                                                               \
+  hipLaunchKernelGGL((k_init<T, B, MODE, int(decltype(K)::value)>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H, \
+                     partials, tc.rows, tc.tiles_j, X)
+
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
-                 double* partials, const TileCfg& tc, hipStream_t s, double sigma, const T* shift, const T* ka,
-                 const T* kb) {
-  if (ka) {
-    PMX_CHECK(shift && kb, "k_init: a diffusion session holds the shift field and both face fields");
-    InitData<T> X;
-    X.shift = shift;
-    X.ka = ka;
-    X.kb = kb;
-    PMX_BLOCK_DISPATCH(tc.block,
-        hipLaunchKernelGGL((k_init<T, B, kInitPlain, 3>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
-                           partials, tc.rows, tc.tiles_j, X));
-  } else if (shift) {
-    InitData<T> X;
-    X.shift = shift;
-    PMX_BLOCK_DISPATCH(tc.block,
-        hipLaunchKernelGGL((k_init<T, B, kInitPlain, 2>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
-                           partials, tc.rows, tc.tiles_j, X));
-  } else if (sigma != 0.0) {
-    InitData<T> X;
-    X.sigma = sigma;
-    PMX_BLOCK_DISPATCH(tc.block,
-        hipLaunchKernelGGL((k_init<T, B, kInitPlain, 1>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
-                           partials, tc.rows, tc.tiles_j, X));
-  } else {
-    PMX_BLOCK_DISPATCH(tc.block,
-        hipLaunchKernelGGL((k_init<T, B, kInitPlain>), dim3(tc.ntiles()), dim3(B), 0, s, G, Tb, w, r, H,
-                           partials, tc.rows, tc.tiles_j, InitData<T>{}));
-  }
+                 double* partials, const TileCfg& tc, hipStream_t s, const OperatorData<T>& op) {
+  InitData<T> X;
+  set_operator(X, op);
+  with_op_kind(op.kind(), [&](auto K) { PMX_BLOCK_DISPATCH(tc.block, PMX_K_INIT(B, kInitPlain, K)); });
   HIP_CHECK(hipGetLastError());
 }
 
@@ -336,33 +318,13 @@ template <typename T>
 void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
                       const TileCfg& tc, const InitData<T>& X, bool measure, hipStream_t s) {
   PMX_CHECK(tc.block == 256, "the data init runs the init tiling (256 columns per tile)");
-  const bool sh = X.sigma != 0.0;
-  if (measure && X.ka)
-    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, 3>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
-                       partials, tc.rows, tc.tiles_j, X);
-  else if (X.ka)
-    hipLaunchKernelGGL((k_init<T, 256, kInitData, 3>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
-                       partials, tc.rows, tc.tiles_j, X);
-  else if (measure && X.shift)
-    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, 2>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
-                       partials, tc.rows, tc.tiles_j, X);
-  else if (X.shift)
-    hipLaunchKernelGGL((k_init<T, 256, kInitData, 2>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
-                       partials, tc.rows, tc.tiles_j, X);
-  else if (measure && sh)
-    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure, 1>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
-                       partials, tc.rows, tc.tiles_j, X);
-  else if (measure)
-    hipLaunchKernelGGL((k_init<T, 256, kInitMeasure>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
-                       partials, tc.rows, tc.tiles_j, X);
-  else if (sh)
-    hipLaunchKernelGGL((k_init<T, 256, kInitData, 1>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
-                       partials, tc.rows, tc.tiles_j, X);
-  else
-    hipLaunchKernelGGL((k_init<T, 256, kInitData>), dim3(tc.ntiles()), dim3(256), 0, s, G, Tb, w, r, H,
-                       partials, tc.rows, tc.tiles_j, X);
+  with_op_kind(OperatorData<T>{X.sigma, X.shift, X.ka, X.kb}.kind(), [&](auto K) {
+    if (measure) PMX_K_INIT(256, kInitMeasure, K);
+    else PMX_K_INIT(256, kInitData, K);
+  });
   HIP_CHECK(hipGetLastError());
 }
+#undef PMX_K_INIT
 
 template <typename T>
 void launch_edge_r(const DevGeom& G, const DevTables& Tb, const T* r, const T* p0, const T* p1,
@@ -394,7 +356,7 @@ void launch_local_allreduce(double* const* bufs, int nranks, int nq, hipStream_t
 
 #define PMX_INST(T)                                                                              \
   template void launch_init<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>, double*,  \
-                               const TileCfg&, hipStream_t, double, const T*, const T*, const T*); \
+                               const TileCfg&, hipStream_t, const OperatorData<T>&);            \
   template void launch_init_data<T>(const DevGeom&, const DevTables&, T*, T*, HaloBufs<T>,       \
                                     double*, const TileCfg&, const InitData<T>&, bool,           \
                                     hipStream_t);                                                 \

@@ -41,32 +41,20 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
   GpuOptions pre = cfg_.opt;
   // a multi-process RCCL run tracks device progress for its hang watchdog (GpuOptions::progress)
   if ((cfg_.comm == CommKind::kRccl || cfg_.comm == CommKind::kIpc) && cfg_.world > 1) pre.progress = 1;
-  UserField react(cfg_.reaction);
-  react.ld = cfg_.reaction_ld;
-  react.on_device = cfg_.reaction_on_device;
-  react.stream = cfg_.reaction_stream;
-  if (react) {
+  const UserField &react = cfg_.reaction, &dif = cfg_.diffusion;
+  if (react || dif) {
     if (cfg_.comm != CommKind::kSelf && cfg_.comm != CommKind::kLocal)
-      throw std::invalid_argument("a reaction field needs a session that owns every subdomain (world 1 or the "
-                                  "local communicator); multi-process transports are not supported");
-    pre.reaction = 1;
-  }
-  UserField dif(cfg_.diffusion);
-  dif.ld = cfg_.diffusion_ld;
-  dif.on_device = cfg_.diffusion_on_device;
-  dif.stream = cfg_.diffusion_stream;
-  if (dif) {
-    if (cfg_.comm != CommKind::kSelf && cfg_.comm != CommKind::kLocal)
-      throw std::invalid_argument("a diffusion field needs a session that owns every subdomain (world 1 or the "
-                                  "local communicator); multi-process transports are not supported");
-    pre.reaction = 1;  // the field state of the shift switch: T(sigma + c), c = 0 without a reaction field
-    pre.diffusion = 1;
+      throw std::invalid_argument(std::string(react ? "a reaction field" : "a diffusion field") +
+                                  " needs a session that owns every subdomain (world 1 or the local communicator); "
+                                  "multi-process transports are not supported");
+    pre.shift_field = 1;  // T(sigma + c), c = 0 without a reaction field
+    pre.diffusion = dif ? 1 : 0;
   }
   GpuOptions base = resolve_options(pre);
   // sigma != 0 or a reaction field: pcg1 on the row march, or std::invalid_argument
   apply_sigma_rules(cfg_.spec, pg_, base);
-  if (react) check_reaction(react);  // before anything is allocated
-  if (dif) check_diffusion(dif);
+  if (react) check_coefficient(react, false);  // before anything is allocated
+  if (dif) check_coefficient(dif, true);
   if (base.algo == -1) {
     HIP_CHECK(hipSetDevice(cfg_.devices[0]));
     size_t free_b = 0, total_b = 0;
@@ -220,136 +208,88 @@ bool Session::direct_rows() const {
 
 void Session::progress(int i, long long out[3]) const { solvers_.at(size_t(i))->progress(out); }
 
-void Session::check_reaction(const UserField& c) const {
+void Session::check_values(std::initializer_list<FieldCheck> fields, int device, hipStream_t s) const {
   const int M = cfg_.spec.M, N = cfg_.spec.N;
-  const int64_t ld = c.ld ? c.ld : N + 1;
-  if (ld < N + 1) throw std::invalid_argument("reaction: row stride below N + 1");
-  bool bad = false;
-  if (c.on_device) {
+  std::vector<int> h(fields.size(), 0);  // device fields: the flag of each
+  auto on_device = [](const FieldCheck& c) { return *c.f && c.f->on_device; };
+  if (std::any_of(fields.begin(), fields.end(), on_device)) {
+    HIP_CHECK(hipSetDevice(device));
+    int* raw = nullptr;  // for the call only
+    HIP_CHECK(hipMalloc(&raw, h.size() * sizeof(int)));
+    const DevPtr<int> flag(raw);
+    HIP_CHECK(hipMemsetAsync(flag.get(), 0, h.size() * sizeof(int), s));
+    size_t q = 0;
+    for (const FieldCheck& c : fields) {
+      if (on_device(c)) launch_value_check(c.rule, c.f->ptr, c.f->stride(N), M, N, flag.get() + q, s);
+      ++q;
+    }
+    HIP_CHECK(hipMemcpyAsync(h.data(), flag.get(), h.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  size_t q = 0;
+  for (const FieldCheck& c : fields) {
+    const bool ok = !*c.f || (c.f->on_device ? h[q] == 0 : field_values_ok(c.f->ptr, c.f->stride(N), M, N, c.rule));
+    if (!ok) throw std::invalid_argument(std::string(c.name) + field_rule_text(c.rule));
+    ++q;
+  }
+}
+
+void Session::check_coefficient(const UserField& f, bool diffusion) const {
+  const std::string name = diffusion ? "diffusion" : "reaction";
+  if (f.stride(cfg_.spec.N) < cfg_.spec.N + 1) throw std::invalid_argument(name + ": row stride below N + 1");
+  if (f.on_device)
     for (int d : cfg_.devices)
       if (d != cfg_.devices[0])
-        throw std::invalid_argument("a device reaction field needs every subdomain of the session on its device");
-    HIP_CHECK(hipSetDevice(cfg_.devices[0]));
-    int* flag = nullptr;  // for the call only
-    int h = 0;
-    HIP_CHECK(hipMalloc(&flag, sizeof(int)));
-    try {
-      HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), c.stream));
-      launch_reaction_check(c.ptr + ld + 1, ld, M - 1, N - 1, flag, c.stream);  // the interior nodes only
-      HIP_CHECK(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-      HIP_CHECK(hipStreamSynchronize(c.stream));
-    } catch (...) {
-      (void)hipStreamSynchronize(c.stream);
-      (void)hipFree(flag);
-      throw;
-    }
-    HIP_CHECK(hipFree(flag));
-    bad = h != 0;
-  } else {
-    for (int i = 1; i <= M - 1 && !bad; ++i)
-      for (int j = 1; j <= N - 1; ++j) {
-        const double v = c.ptr[int64_t(i) * ld + j];
-        if (!(v >= 0.0) || std::isinf(v)) {
-          bad = true;
-          break;
-        }
-      }
-  }
-  if (bad) throw std::invalid_argument("reaction must be finite and >= 0 on every interior node");
+        throw std::invalid_argument("a device " + name + " field needs every subdomain of the session on its device");
+  check_values({{&f, diffusion ? FieldRule::kPositive : FieldRule::kNonNegInterior, name.c_str()}}, cfg_.devices[0],
+               f.stream);
 }
 
 void Session::upload_reaction(const UserField& c) {
-  const int64_t ld = c.ld ? c.ld : cfg_.spec.N + 1;
   // a device field on its producer's stream (ordered after its producer, no event needed); every solver
   // returns once that stream has consumed the field
-  for (auto& sp : solvers_) sp->set_reaction(c.ptr, ld, c.on_device, c.on_device ? c.stream : nullptr);
-}
-
-void Session::set_reaction(const UserField& c) {
-  if (!has_reaction())
-    throw std::invalid_argument("set_reaction needs a session built with a reaction field (make_session(p, "
-                                "reaction=c)): sessions without one hold no shift field");
-  if (!c) throw std::invalid_argument("set_reaction: no field given");
-  check_reaction(c);
-  if (!drivers_.empty()) synchronize();  // no sweep in flight reads the field
-  upload_reaction(c);
-  stale_ = true;
-}
-
-void Session::check_diffusion(const UserField& k) const {
-  const int M = cfg_.spec.M, N = cfg_.spec.N;
-  const int64_t ld = k.ld ? k.ld : N + 1;
-  if (ld < N + 1) throw std::invalid_argument("diffusion: row stride below N + 1");
-  bool bad = false;
-  if (k.on_device) {
-    for (int d : cfg_.devices)
-      if (d != cfg_.devices[0])
-        throw std::invalid_argument("a device diffusion field needs every subdomain of the session on its device");
-    HIP_CHECK(hipSetDevice(cfg_.devices[0]));
-    int* flag = nullptr;  // for the call only
-    int h = 0;
-    HIP_CHECK(hipMalloc(&flag, sizeof(int)));
-    try {
-      HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(int), k.stream));
-      launch_diffusion_check(k.ptr, ld, M + 1, N + 1, flag, k.stream);  // every node
-      HIP_CHECK(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, k.stream));
-      HIP_CHECK(hipStreamSynchronize(k.stream));
-    } catch (...) {
-      (void)hipStreamSynchronize(k.stream);
-      (void)hipFree(flag);
-      throw;
-    }
-    HIP_CHECK(hipFree(flag));
-    bad = h != 0;
-  } else {
-    for (int i = 0; i <= M && !bad; ++i)
-      for (int j = 0; j <= N; ++j) {
-        const double v = k.ptr[int64_t(i) * ld + j];
-        if (!(v > 0.0) || std::isinf(v)) {
-          bad = true;
-          break;
-        }
-      }
-  }
-  if (bad) throw std::invalid_argument("diffusion must be finite and > 0 on every node");
+  for (auto& sp : solvers_)
+    sp->set_reaction(c.ptr, c.stride(cfg_.spec.N), c.on_device, c.on_device ? c.stream : nullptr);
 }
 
 void Session::upload_diffusion(const UserField& k) {
   const int M = cfg_.spec.M, N = cfg_.spec.N;
-  const int64_t ld = k.ld ? k.ld : N + 1;
   for (auto& sp : solvers_) {
     if (k.on_device) {  // on its producer's stream; the solver returns once that stream has consumed the field
-      sp->set_diffusion(k.ptr, ld, k.stream);
+      sp->set_diffusion(k.ptr, k.stride(N), k.stream);
       continue;
     }
     HIP_CHECK(hipSetDevice(sp->device()));
     double* raw = nullptr;  // for this subdomain's kernel only
     HIP_CHECK(hipMalloc(&raw, size_t(M + 1) * size_t(N + 1) * sizeof(double)));
     const DevPtr<double> tmp(raw);
-    HIP_CHECK(hipMemcpy2D(tmp.get(), size_t(N + 1) * sizeof(double), k.ptr, size_t(ld) * sizeof(double),
+    HIP_CHECK(hipMemcpy2D(tmp.get(), size_t(N + 1) * sizeof(double), k.ptr, size_t(k.stride(N)) * sizeof(double),
                           size_t(N + 1) * sizeof(double), size_t(M + 1), hipMemcpyHostToDevice));
     sp->set_diffusion(tmp.get(), N + 1, nullptr);
   }
 }
 
-void Session::set_diffusion(const UserField& k) {
-  if (!has_diffusion())
-    throw std::invalid_argument("set_diffusion needs a session built with a diffusion field (make_session(p, "
-                                "diffusion=k)): sessions without one hold no face-coefficient fields");
-  if (!k) throw std::invalid_argument("set_diffusion: no field given");
-  check_diffusion(k);
+void Session::set_coefficient(const UserField& f, bool diffusion) {
+  const std::string name = diffusion ? "diffusion" : "reaction";
+  if (!(diffusion ? has_diffusion() : has_reaction()))
+    throw std::invalid_argument("set_" + name + " needs a session built with a " + name + " field (make_session(p, " +
+                                name + (diffusion ? "=k" : "=c") + ")): sessions without one hold no " +
+                                (diffusion ? "face-coefficient fields" : "shift field"));
+  if (!f) throw std::invalid_argument("set_" + name + ": no field given");
+  check_coefficient(f, diffusion);
   if (!drivers_.empty()) synchronize();  // no sweep in flight reads the fields
-  upload_diffusion(k);
+  if (diffusion) upload_diffusion(f);
+  else upload_reaction(f);
   stale_ = true;
 }
 
+void Session::set_reaction(const UserField& c) { set_coefficient(c, false); }
+void Session::set_diffusion(const UserField& k) { set_coefficient(k, true); }
+
 ErrorStats Session::error_norms() {
-  if (has_diffusion())
-    throw std::invalid_argument("error_norms: the closed-form solution does not solve a problem with a diffusion "
-                                "field; compare the solution with your own (PoissonEllipse.error_norms(w, exact=u))");
-  if (has_reaction())
-    throw std::invalid_argument("error_norms: the closed-form solution does not solve a problem with a reaction "
-                                "field; compare the solution with your own (PoissonEllipse.error_norms(w, exact=u))");
+  if (const char* noun = field_noun())
+    throw std::invalid_argument(std::string("error_norms: the closed-form solution does not solve a problem with ") +
+                                noun + "; compare the solution with your own (PoissonEllipse.error_norms(w, exact=u))");
   if (cfg_.spec.sigma != 0.0)
     throw std::invalid_argument("error_norms: the closed-form solution holds for sigma = 0 only; compare the "
                                 "solution with your own (PoissonEllipse.error_norms(w, exact=u))");
@@ -394,30 +334,9 @@ void Session::wait_for(hipStream_t producer) {
 }
 
 void Session::check_finite(const UserField& rhs, const UserField& w0) {
-  const UserField* f[2] = {&rhs, &w0};
-  const char* name[2] = {"rhs", "w0"};
-  if (!(rhs && rhs.on_device) && !(w0 && w0.on_device)) return;
-  HIP_CHECK(hipSetDevice(require_one_device()));
-  const hipStream_t s = stream_of(0);
-  const int rows = cfg_.spec.M + 1, cols = cfg_.spec.N + 1;
-  int* flag = nullptr;  // one per field, for the call only
-  int h[2] = {0, 0};
-  HIP_CHECK(hipMalloc(&flag, sizeof(h)));
-  try {
-    HIP_CHECK(hipMemsetAsync(flag, 0, sizeof(h), s));
-    for (int q = 0; q < 2; ++q)
-      if (*f[q] && f[q]->on_device)
-        launch_finite_check(f[q]->ptr, f[q]->ld ? f[q]->ld : cols, rows, cols, flag + q, s);
-    HIP_CHECK(hipMemcpyAsync(h, flag, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(flag);
-    throw;
-  }
-  HIP_CHECK(hipFree(flag));
-  for (int q = 0; q < 2; ++q)
-    if (h[q]) throw std::invalid_argument(std::string(name[q]) + " holds non-finite values");
+  const UserField none, &f = rhs.on_device ? rhs : none, &w = w0.on_device ? w0 : none;  // host fields: the caller's
+  if (!f && !w) return;
+  check_values({{&f, FieldRule::kFinite, "rhs"}, {&w, FieldRule::kFinite, "w0"}}, require_one_device(), stream_of(0));
 }
 
 void Session::stage_init_data(const UserField& rhs, const UserField& w0) {
@@ -434,7 +353,7 @@ void Session::stage_init_data(const UserField& rhs, const UserField& w0) {
   // every subdomain reads its block straight out of the global arrays (row stride N + 1 unless the
   // field says otherwise): f from its first owned node, w0 one node earlier in both directions, i.e.
   // with its ring -- the neighbours' values, so nothing is exchanged for w0
-  const int64_t ldf = rhs.ld ? rhs.ld : cfg_.spec.N + 1, ldw = w0.ld ? w0.ld : cfg_.spec.N + 1;
+  const int64_t ldf = rhs.stride(cfg_.spec.N), ldw = w0.stride(cfg_.spec.N);
   for (auto& sp : solvers_) {
     const Subdomain& sd = sp->sd();
     // local (0, 0) of w0, the first owned node of rhs
@@ -472,7 +391,7 @@ double Session::residual_norm(const UserField& rhs) {
     check_finite(rhs, UserField());
   }
   GpuSubdomainSolver& g = *solvers_[0];
-  const int64_t ld = rhs.ld ? rhs.ld : cfg_.spec.N + 1;  // the owned nodes start at global (1, 1)
+  const int64_t ld = rhs.stride(cfg_.spec.N);  // the owned nodes start at global (1, 1)
   const GridInfo gi(cfg_.spec);
   return std::sqrt(gi.h1h2 * g.residual_sumsq(rhs ? rhs.ptr + ld + 1 : nullptr, stream_of(0), ld, rhs.on_device));
 }
@@ -518,7 +437,7 @@ void Session::apply_device(const UserField& x, const UserField& out, const UserF
   }
   if (!(std::isfinite(alpha) && std::isfinite(beta) && std::isfinite(gamma) && std::isfinite(c0)))
     throw std::invalid_argument("apply: alpha, beta, gamma and const must be finite");
-  auto ld = [&](const UserField& f) { return f.ld ? f.ld : int64_t(N) + 1; };
+  auto ld = [&](const UserField& f) { return f.stride(N); };
   auto span = [&](const UserField& f) { return (int64_t(M) * ld(f) + N + 1) * int64_t(sizeof(double)); };
   const char *xb = reinterpret_cast<const char*>(x.ptr), *ob = reinterpret_cast<const char*>(out.ptr);
   if (xb < ob + span(out) && ob < xb + span(x)) throw std::invalid_argument("apply: out overlaps x");
@@ -532,15 +451,12 @@ void Session::apply_device(const UserField& x, const UserField& out, const UserF
   if (y && y.stream != x.stream) wait_for(y.stream);
   if (out.stream != x.stream && !(y && out.stream == y.stream)) wait_for(out.stream);
   ApplyCoef K;
-  K.alpha = alpha; K.beta = beta; K.gamma = y ? gamma : 0.0; K.c0 = c0; K.sigma = cfg_.spec.sigma;
+  K.alpha = alpha; K.beta = beta; K.gamma = y ? gamma : 0.0; K.c0 = c0;
   K.plain = alpha == 1.0 && beta == 0.0 && !y && c0 == 0.0;
   for (size_t i = 0; i < solvers_.size(); ++i) {
-    if (has_diffusion()) {  // ... and its face-coefficient fields, in the tables' place
-      K.ka = solvers_[i]->face_base(0);
-      K.kb = solvers_[i]->face_base(1);
-    }
-    if (has_reaction() || has_diffusion()) {  // the owning subdomain's shift field, in sigma's place
-      K.shift = solvers_[i]->shift_base();
+    // sigma, or the owning subdomain's shift field in its place and its face-coefficient fields in the tables'
+    set_operator(K, solvers_[i]->op<void>());
+    if (K.shift) {
       K.spitch = solvers_[i]->pitch();
       K.sgi0 = solvers_[i]->sd().gi0();
       K.sgj0 = solvers_[i]->sd().gj0();
@@ -651,12 +567,9 @@ std::vector<double> Session::gather_local_w() {
 }
 
 void Session::require_no_sigma(const char* what) const {
-  if (has_diffusion())
-    throw std::invalid_argument(std::string(what) + ": checkpoint files do not record a diffusion field (format "
-                                "v7); sessions with one cannot be checkpointed");
-  if (has_reaction())
-    throw std::invalid_argument(std::string(what) + ": checkpoint files do not record a reaction field (format "
-                                "v7); sessions with one cannot be checkpointed");
+  if (const char* noun = field_noun())
+    throw std::invalid_argument(std::string(what) + ": checkpoint files do not record " + noun +
+                                " (format v7); sessions with one cannot be checkpointed");
   if (cfg_.spec.sigma != 0.0)
     throw std::invalid_argument(std::string(what) + ": checkpoint files do not record sigma (format v7); "
                                 "sessions with sigma != 0 cannot be checkpointed");

@@ -169,13 +169,14 @@ struct GpuOptions {
   // which probed block to keep: 0 the fastest (default), 1 the slowest -- for slow-class A/Bs and
   // counter tables on one box (PMX_PLACEMENT_PICK=slowest)
   int placement_pick = 0;
-  // The session solves with a reaction field c(x, y) (Session's `reaction`): every solver allocates the shift
-  // field T(sigma + c) (MemoryPlan::nshift) and runs the field state of the shift switch, under the rules of
-  // the screened problem (apply_sigma_rules).  Set by the Session; the values arrive through set_reaction.
-  int reaction = 0;
+  // The session solves with a reaction field c(x, y) or a diffusion field (Session's `reaction`, `diffusion`):
+  // every solver allocates the shift field T(sigma + c) (MemoryPlan::nshift; c = 0 without a reaction field) and
+  // runs the field state of the shift switch, under the rules of the screened problem (apply_sigma_rules).  Set
+  // by the Session; the values arrive through set_reaction.
+  int shift_field = 0;
   // The session solves with a diffusion field k(x, y) (Session's `diffusion`): every solver allocates the two
   // face-coefficient fields (MemoryPlan::ndiff) next to the shift field -- a diffusion session always runs
-  // the field state of the shift switch, so `reaction` is set with it -- and runs the diffusion sweeps, in
+  // the field state of the shift switch, so `shift_field` is set with it -- and runs the diffusion sweeps, in
   // fp64 registers for either storage type.  Set by the Session; the values arrive through set_diffusion.
   int diffusion = 0;
   bool resolved = false;  // environment overrides already applied (resolve_options)
@@ -209,7 +210,7 @@ constexpr int64_t kCaAutoPoints = 6000000;
 // The screened problem (ProblemSpec::sigma != 0) runs pcg1 on the row march only.  Turns auto choices
 // into that (algo 1 at any grid size, block tiles off) and throws std::invalid_argument, naming the
 // option, for an explicit s-step / pcg2 / exact arithmetic / block tiles.  No-op with sigma == 0.
-// A reaction field (GpuOptions::reaction) falls under the same rules at any sigma.
+// A shift field (GpuOptions::shift_field) falls under the same rules at any sigma.
 // Called before anything is allocated (Session, GpuSubdomainSolver).
 void apply_sigma_rules(const ProblemSpec& spec, const ProcGrid& grid, GpuOptions& resolved);
 int choose_algo(const ProblemSpec& spec, const ProcGrid& grid, const GpuOptions& resolved, double device_total_bytes,
@@ -294,7 +295,7 @@ class GpuSubdomainSolver {
   // every reduction and all-reduce of it.  No-op under the step rule.
   void enqueue_stop_init(hipStream_t s);
   bool has_init_data() const { return !stage_f_.empty() || !stage_w_.empty() || dev_f_ || dev_w_; }
-  // Solvers built with GpuOptions::reaction: (re)fill the shift field with T(sigma + c), rounded once, from
+  // Solvers built with GpuOptions::shift_field: (re)fill the shift field with T(sigma + c), rounded once, from
   // the global (M+1) x (N+1) fp64 array c (row stride ld) -- this subdomain's block with its radius-2 frame,
   // since decomposed pcg1 recomputes p, A p and z on the ghost diamond; nodes of the box boundary and beyond
   // are never read and hold 0.  on_device: c is memory of this solver's device, read by the scatter kernel on
@@ -302,7 +303,7 @@ class GpuSubdomainSolver {
   // address never changes, so captured graphs stay valid; the values are static, so nothing is exchanged.
   // The iteration state belongs to the old operator afterwards: the next init starts the new one.
   void set_reaction(const double* c, int64_t ld, bool on_device, hipStream_t s);
-  bool has_reaction() const { return plan_.nshift != 0; }
+  bool has_shift_field() const { return plan_.nshift != 0; }
   // Solvers built with GpuOptions::diffusion: (re)fill the face-coefficient fields from the nodal values k, a
   // global (M+1) x (N+1) fp64 array in memory of this solver's device (row stride ld), by one kernel on s
   // (launch_face_fields: this subdomain's block with its radius-2 frame plus the extra row and column; cells
@@ -314,6 +315,11 @@ class GpuSubdomainSolver {
   const void* face_base(int f) const { return plan_.ndiff ? field_ptr(plan_.diff_field(f)) : nullptr; }
   // the shift field at local (0, 0) in the storage type; nullptr without a reaction field
   const void* shift_base() const { return plan_.nshift ? field_ptr(plan_.shift_field()) : nullptr; }
+  // the operator of this subdomain: sigma, and the fields above in the storage type T (void: type-erased)
+  template <typename T> OperatorData<T> op() const {
+    return {spec_.sigma, static_cast<const T*>(shift_base()), static_cast<const T*>(face_base(0)),
+            static_cast<const T*>(face_base(1))};
+  }
   int64_t pitch() const { return plan_.pitch; }
   size_t elem_bytes() const { return plan_.elem; }
   // sum over the owned nodes of (B - A w)^2 for the current w (pending steps applied, as
@@ -484,8 +490,6 @@ class GpuSubdomainSolver {
     auto at = [&](int f) { return reinterpret_cast<T*>(field_ptr(f)); };
     return {at(0), at(1), plan_.nfields == 5 ? at(4) : nullptr, at(2), at(3)};
   }
-  template <typename T> const T* shift() const { return static_cast<const T*>(shift_base()); }
-  template <typename T> const T* face(int f) const { return static_cast<const T*>(face_base(f)); }
   template <typename T> HaloBufs<T> halo() const;
   template <typename T> void init_impl(hipStream_t s);
   template <typename T> void kernel_a(hipStream_t s, int part = 0);  // k_pcg_a, or the pcg1 sweep

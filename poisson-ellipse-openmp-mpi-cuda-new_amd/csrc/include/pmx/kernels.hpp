@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "pmx/device_types.hpp"
+#include "pmx/operator.hpp"
 
 namespace pmx {
 
@@ -84,9 +85,8 @@ enum AblBits : int {
 
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
-                 double* partials, const TileCfg& tc, hipStream_t s, double sigma = 0.0,
-                 const T* shift = nullptr,  // shift: as InitData::shift
-                 const T* ka = nullptr, const T* kb = nullptr);  // as InitData::ka / kb
+                 double* partials, const TileCfg& tc, hipStream_t s,
+                 const OperatorData<T>& op = {});  // op.kind() picks the kernel (as InitData's last four members)
 
 // k_init with data (GpuSubdomainSolver::set_init_data / residual_norm), on launch_init's tiling.
 //   data init (measure = false): r holds f on the owned nodes (has_f; else the constant G.F), w holds
@@ -162,10 +162,8 @@ size_t pcg1_order_slots(const TileCfg& tc);  // d_order capacity pcg1_build_orde
 template <typename T>
 void launch_pcg1(const DevGeom& G, const DevTables& Tb, T* w, T* r, T* r2, T* p0, T* p1,
                  double* partials, PcgState* S, const TileCfg& tc, hipStream_t s, int part = 0,
-                 bool wsweep = false, double sigma = 0.0,  // sigma: ProblemSpec::sigma (!= 0: the SH sweeps)
-                 const T* shift = nullptr,  // the shift field of a reaction session (the field sweeps), else null
-                 // the face-coefficient fields of a diffusion session (the diffusion sweeps; with shift), else null
-                 const T* ka = nullptr, const T* kb = nullptr);
+                 bool wsweep = false,
+                 const OperatorData<T>& op = {});  // op.kind() picks the sigma, field or diffusion sweeps
 
 // pcg1 sweep with block tiles (pcg1_block.hip): one workgroup per tc.rows x 124 tile, the three
 // pipeline stages row-parallel; undecomposed fp64 grids; partial sums per tile as k_pcg1.  With a ticket the sweep also finishes the reduction (red_c =
@@ -322,16 +320,14 @@ int launch_error_norms(const DevGeom& G, const DevTables& Tb, const T* w, const 
 // rows x cols of src -> dst (row stride pitch), rounded to T as the host staging rounds
 template <typename T>
 void launch_scatter(const double* src, int64_t ld, T* dst, int64_t pitch, int rows, int cols, hipStream_t s);
-// *flag <- 1 if any of the rows x cols values is not finite (the caller zeroes it first)
-void launch_finite_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s);
-// A reaction field (io_kernels.hip).  launch_scatter with dst = T(sigma + src), rounded once; and the check of
-// its values: *flag <- 1 for a NaN, an infinity or a negative value among the rows x cols values
+// *flag <- 1 if a value of the global (M+1) x (N+1) array `field` breaks `rule` (the caller zeroes it first): one
+// of k_finite, k_reaction_check and k_diffusion_check over the nodes field_values_ok reads
+void launch_value_check(FieldRule rule, const double* field, int64_t ld, int M, int N, int* flag, hipStream_t s);
+// A reaction field (io_kernels.hip).  launch_scatter with dst = T(sigma + src), rounded once
 template <typename T>
 void launch_scatter_shift(const double* src, int64_t ld, T* dst, int64_t pitch, int rows, int cols, double sigma,
                           hipStream_t s);
-void launch_reaction_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s);
-// A diffusion field (io_kernels.hip).  The check of its values: *flag <- 1 for a NaN, an infinity or a value
-// <= 0 among the rows x cols values.  And the face-coefficient fields of one subdomain from the nodal values
+// A diffusion field (io_kernels.hip).  The face-coefficient fields of one subdomain from the nodal values
 // k (global (M+1) x (N+1), row stride ld, device memory) and the 1-D tables:
 //   ak(li, lj) = T((0.5 (k[gi-1, gj] + k[gi, gj])) a(gi, gj)),  bk(li, lj) = T((0.5 (k[gi, gj-1] + k[gi, gj])) b(gi, gj))
 // in fp64, rounded once, with a / b the exact face formulas (coef_a / coef_b, as the s-step's face fields);
@@ -339,7 +335,6 @@ void launch_reaction_check(const double* src, int64_t ld, int rows, int cols, in
 // G.pitch; written: local rows -1 .. nx+3 of ak, -1 .. nx+2 of bk, columns -1 .. G.pitch-2 (the whole row).
 template <typename T>
 void launch_face_fields(const DevGeom& G, const DevTables& Tb, const double* k, int64_t ld, T* ak, T* bk, hipStream_t s);
-void launch_diffusion_check(const double* src, int64_t ld, int rows, int cols, int* flag, hipStream_t s);
 // local nodes (li0 .. li0+rows-1) x (lj0 .. lj0+cols-1) of a subdomain with local (0, 0) at global
 // (gi0, gj0) -> out[gi * ld + gj]: w + ca pa (+ cb pb) as launch_error_norms forms it (w, pa, pb point to
 // local (0, 0), row stride pitch); nodes on the global boundary (gi in {0, M}, gj in {0, N}) get zero

@@ -2,6 +2,7 @@
 // Shared by the C++ CLI (apps/pmx.cpp) and the Python bindings.
 #pragma once
 
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -12,6 +13,23 @@
 namespace pmx {
 
 enum class CommKind : int { kSelf = 0, kLocal = 1, kRccl = 2, kIpc = 3, kLoopback = 4 };
+
+// A global (M+1) x (N+1) fp64 field handed to a session: host memory, or memory of the session's
+// device.  ld: the row stride in elements (0: dense, N + 1); the column stride is 1.
+// A device field follows stream order without any synchronisation by the caller.  An input is read
+// after the work enqueued on `stream` (its producer's) before the call: the session records an event
+// there and its own streams wait for it.  An output is complete for work enqueued on `stream` after
+// the call: `stream` waits for an event of every session stream that wrote it.
+struct UserField {
+  const double* ptr = nullptr;
+  int64_t ld = 0;
+  bool on_device = false;
+  hipStream_t stream = nullptr;
+  UserField() = default;
+  UserField(const double* host) : ptr(host) {}  // a dense host array
+  explicit operator bool() const { return ptr != nullptr; }
+  int64_t stride(int N) const { return ld ? ld : int64_t(N) + 1; }  // the row stride in elements
+};
 
 struct SessionConfig {
   ProblemSpec spec;
@@ -38,39 +56,17 @@ struct SessionConfig {
   // the device it shares (choose_algo; the torch path's comm_layout(sharing=...) likewise).
   int sharing = 0;
   // Reaction field c(x, y) >= 0: the session solves (A + (sigma + c) I) u = f.  A global (M+1) x (N+1) fp64
-  // array (UserField below: host or device memory; box-boundary values are ignored and never read), consumed
+  // array (host or device memory; box-boundary values are ignored and never read), consumed
   // by the constructor.  Runs under the screened problem's rules (apply_sigma_rules) on sessions that own
   // every subdomain; std::invalid_argument, before anything is allocated, otherwise and for a NaN, an
   // infinity or a negative value on an interior node.
-  const double* reaction = nullptr;
-  int64_t reaction_ld = 0;
-  bool reaction_on_device = false;
-  hipStream_t reaction_stream = nullptr;
+  UserField reaction;
   // Diffusion field k(x, y): the session solves (-div(k grad) + sigma + c) u = f.  Nodal values, a global
   // (M+1) x (N+1) fp64 array like `reaction`, but finite and > 0 on EVERY node: the faces next to the box
   // boundary read the boundary values.  Every subdomain keeps the two face-coefficient fields
   // (GpuSubdomainSolver::set_diffusion) and the shift field (filled with sigma when there is no reaction
   // field).  The rules and refusals of `reaction` apply.
-  const double* diffusion = nullptr;
-  int64_t diffusion_ld = 0;
-  bool diffusion_on_device = false;
-  hipStream_t diffusion_stream = nullptr;
-};
-
-// A global (M+1) x (N+1) fp64 field handed to a session: host memory, or memory of the session's
-// device.  ld: the row stride in elements (0: dense, N + 1); the column stride is 1.
-// A device field follows stream order without any synchronisation by the caller.  An input is read
-// after the work enqueued on `stream` (its producer's) before the call: the session records an event
-// there and its own streams wait for it.  An output is complete for work enqueued on `stream` after
-// the call: `stream` waits for an event of every session stream that wrote it.
-struct UserField {
-  const double* ptr = nullptr;
-  int64_t ld = 0;
-  bool on_device = false;
-  hipStream_t stream = nullptr;
-  UserField() = default;
-  UserField(const double* host) : ptr(host) {}  // a dense host array
-  explicit operator bool() const { return ptr != nullptr; }
+  UserField diffusion;
 };
 
 class Session {
@@ -124,12 +120,12 @@ class Session {
   // (GpuSubdomainSolver::set_reaction) -- same addresses, so the captured graphs stay valid.  The iteration
   // state belongs to the old operator afterwards: step() throws until the next init() / solve().
   void set_reaction(const UserField& c);
-  bool has_reaction() const { return cfg_.reaction != nullptr; }
+  bool has_reaction() const { return bool(cfg_.reaction); }
   // Replace the diffusion field of a session built with one (SessionConfig::diffusion): as set_reaction --
   // checked before the session is touched, the face-coefficient fields rewritten in place, step() throws
   // until the next init() / solve().
   void set_diffusion(const UserField& k);
-  bool has_diffusion() const { return cfg_.diffusion != nullptr; }
+  bool has_diffusion() const { return bool(cfg_.diffusion); }
   void step(int64_t n);
   void synchronize();
   RunStats solve(int poll_batches = 1);
@@ -191,18 +187,31 @@ class Session {
   int require_one_device() const;        // the device every solver lives on (device fields need one)
   void wait_for(hipStream_t producer);   // every session stream waits for `producer`'s work so far
   void hand_over(hipStream_t consumer);  // `consumer` waits for every session stream's work so far
-  // throws std::invalid_argument naming the first device field with a non-finite value
+  // One field under its value rule (pmx/operator.hpp); name: what the refusal calls it
+  struct FieldCheck {
+    const UserField* f;
+    FieldRule rule;
+    const char* name;
+  };
+  // throws std::invalid_argument ("<name>" + field_rule_text) for the first field of the list that breaks its
+  // rule.  Host fields: field_values_ok.  Device fields (memory of `device`): one flag each in one allocation,
+  // one launch_value_check each on s, one copy back and one synchronise.  Empty fields are skipped.
+  void check_values(std::initializer_list<FieldCheck> fields, int device, hipStream_t s) const;
+  // the device fields among rhs and w0, on stream_of(0)
   void check_finite(const UserField& rhs, const UserField& w0);
-  // throws std::invalid_argument unless c is finite and >= 0 on every interior node (a device field: one
-  // k_reaction_check launch on its producer's stream)
-  void check_reaction(const UserField& c) const;
+  // a reaction field (diffusion: a diffusion field) of the constructor or a set_*: its row stride, then its
+  // values -- a device field on its producer's stream, and only with every subdomain on its device
+  void check_coefficient(const UserField& f, bool diffusion) const;
+  // set_reaction / set_diffusion: the field checked, the session idle, the upload, the iteration state stale
+  void set_coefficient(const UserField& f, bool diffusion);
   void upload_reaction(const UserField& c);
-  // throws std::invalid_argument unless k is finite and > 0 on every node (a device field: one
-  // k_diffusion_check launch over the whole tensor on its producer's stream)
-  void check_diffusion(const UserField& k) const;
   // a host field goes up whole to a temporary device copy per subdomain, so that one kernel forms the face
   // fields from either source (the same bits)
   void upload_diffusion(const UserField& k);
+  // what the refusals call the session's coefficient field; nullptr without one
+  const char* field_noun() const {
+    return has_diffusion() ? "a diffusion field" : has_reaction() ? "a reaction field" : nullptr;
+  }
   bool stale_ = false;  // set_reaction since the last init: the iteration state is the old operator's
 
   SessionConfig cfg_;

@@ -13,6 +13,7 @@
 #include "pmx/decomp.hpp"
 #include "pmx/geometry.hpp"
 #include "pmx/memory_plan.hpp"
+#include "pmx/operator.hpp"
 #include "pmx/report.hpp"
 #include "pmx/spec.hpp"
 
@@ -185,6 +186,78 @@ void test_memory_plan() {
             }
 }
 
+// the operator members of InitData<double> and ApplyCoef (HIP headers), as set_operator fills them
+struct InitData4 {
+  double sigma = 0.0;
+  const double *shift = nullptr, *ka = nullptr, *kb = nullptr;
+};
+
+// OperatorData::kind(): the one rule that picks the kernels, and k_pcg1's (SH, DIF) pair
+void test_operator_kind() {
+  const double f[3] = {0.0, 0.0, 0.0};
+  using Op = OperatorData<double>;
+  CHECK((Op{}.kind() == OpKind::kPlain));
+  CHECK((Op{2.5, nullptr, nullptr, nullptr}.kind() == OpKind::kSigma));
+  CHECK((Op{0.0, f, nullptr, nullptr}.kind() == OpKind::kField));
+  CHECK((Op{2.5, f, nullptr, nullptr}.kind() == OpKind::kField));
+  CHECK((Op{0.0, f, f + 1, f + 2}.kind() == OpKind::kDiffusion));
+  CHECK((Op{2.5, f, f + 1, f + 2}.kind() == OpKind::kDiffusion));
+  CHECK((OperatorData<void>{0.0, f, f, f}.kind() == OpKind::kDiffusion));  // type-erased, as ApplyCoef
+  for (const Op& bad : {Op{0.0, nullptr, f, f}, Op{0.0, f, f, nullptr}, Op{1.0, nullptr, f, nullptr}}) {
+    bool threw = false;
+    try { (void)bad.kind(); } catch (const Error&) { threw = true; }
+    CHECK(threw);
+  }
+  // the enum's values are the SH of k_init and k_apply; k_pcg1 takes SH = min(kind, 2) and DIF = (kind == 3)
+  CHECK(int(OpKind::kPlain) == 0 && int(OpKind::kSigma) == 1 && int(OpKind::kField) == 2 && int(OpKind::kDiffusion) == 3);
+  const struct { OpKind k; int sh; bool dif; } map[] = {{OpKind::kPlain, 0, false}, {OpKind::kSigma, 1, false},
+                                                        {OpKind::kField, 2, false}, {OpKind::kDiffusion, 2, true}};
+  for (const auto& m : map) {
+    CHECK(pcg1_sh(m.k) == m.sh && pcg1_dif(m.k) == m.dif);
+    CHECK(with_op_kind(m.k, [](auto K) { return decltype(K)::value; }) == m.k);
+  }
+  InitData4 x;
+  set_operator(x, Op{2.5, f, f + 1, f + 2});
+  CHECK(x.sigma == 2.5 && x.shift == f && x.ka == f + 1 && x.kb == f + 2);
+}
+
+// field_values_ok on 5 x 6 nodes (M = 4, N = 5) with row stride 8: the padding holds NaN and is never read
+void test_field_values() {
+  const int M = 4, N = 5, ld = 8;
+  const double inf = HUGE_VAL, nan = std::nan("");
+  std::vector<double> clean(size_t(M + 1) * ld, nan);
+  for (int i = 0; i <= M; ++i)
+    for (int j = 0; j <= N; ++j) clean[size_t(i) * ld + j] = 1.0 + 0.25 * i + 0.125 * j;
+  const FieldRule rules[3] = {FieldRule::kFinite, FieldRule::kNonNegInterior, FieldRule::kPositive};
+  for (FieldRule r : rules) CHECK(field_values_ok(clean.data(), ld, M, N, r));
+  // value -> passes {kFinite, kNonNegInterior, kPositive} where the rule reads the node
+  const struct { double v; bool ok[3]; } vals[] = {{nan, {false, false, false}}, {inf, {false, false, false}},
+                                                   {-1.0, {true, false, false}}, {0.0, {true, true, false}},
+                                                   {-0.0, {true, true, false}}};
+  const int interior[][2] = {{1, 1}, {2, 3}, {M - 1, N - 1}};
+  const int boundary[][2] = {{0, 0}, {0, 2}, {2, 0}, {M, 3}, {1, N}, {M, N}};
+  for (const auto& t : vals) {
+    for (const auto& n : interior) {
+      std::vector<double> a = clean;
+      a[size_t(n[0]) * ld + n[1]] = t.v;
+      for (int r = 0; r < 3; ++r) CHECK(field_values_ok(a.data(), ld, M, N, rules[r]) == t.ok[r]);
+    }
+    for (const auto& n : boundary) {  // kNonNegInterior never reads the box boundary
+      std::vector<double> a = clean;
+      a[size_t(n[0]) * ld + n[1]] = t.v;
+      CHECK(field_values_ok(a.data(), ld, M, N, FieldRule::kFinite) == t.ok[0]);
+      CHECK(field_values_ok(a.data(), ld, M, N, FieldRule::kNonNegInterior));
+      CHECK(field_values_ok(a.data(), ld, M, N, FieldRule::kPositive) == t.ok[2]);
+    }
+  }
+  CHECK(field_values_ok(clean.data(), ld, M, N, FieldRule::kFinite));  // (the copies were the ones changed)
+  CHECK(std::string("rhs") + field_rule_text(FieldRule::kFinite) == "rhs holds non-finite values");
+  CHECK(std::string("reaction") + field_rule_text(FieldRule::kNonNegInterior) ==
+        "reaction must be finite and >= 0 on every interior node");
+  CHECK(std::string("diffusion") + field_rule_text(FieldRule::kPositive) ==
+        "diffusion must be finite and > 0 on every node");
+}
+
 }  // namespace
 
 int main() {
@@ -195,6 +268,8 @@ int main() {
   test_report_formats();
   test_spec_validation();
   test_memory_plan();
+  test_operator_kind();
+  test_field_values();
   std::printf("pmx_unit_tests: %d checks, %d failed\n", g_checks, g_failed);
   return g_failed ? 1 : 0;
 }

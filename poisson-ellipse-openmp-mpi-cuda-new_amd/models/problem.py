@@ -148,16 +148,7 @@ class PoissonEllipse:
         device tensor and for non-finite values (the native entry points apply the same rules)."""
         if a is None:
             return None
-        if hasattr(a, "numpy") and hasattr(a, "device"):  # a torch tensor
-            if a.device.type != "cpu":
-                raise ValueError(f"{name}: device tensors are not supported, pass a NumPy array or a CPU tensor")
-            a = a.detach().numpy()
-        if not isinstance(a, np.ndarray):
-            raise ValueError(f"{name} must be a NumPy array or a CPU torch tensor")
-        if a.dtype != np.float64:
-            raise ValueError(f"{name} must have dtype float64, got {a.dtype}")
-        if a.shape != (self.M + 1, self.N + 1):
-            raise ValueError(f"{name} must have shape (M+1, N+1) = {(self.M + 1, self.N + 1)}, got {a.shape}")
+        a = self._host_array(a, name, apply_hint=False)
         if not np.isfinite(a).all():
             raise ValueError(f"{name} holds non-finite values")
         return np.ascontiguousarray(a)
@@ -185,12 +176,13 @@ class PoissonEllipse:
             raise ValueError(f"{name} must be finite and > 0 on every node")
         return np.ascontiguousarray(a)
 
-    def _host_array(self, a, name: str, writable: bool = False) -> np.ndarray:
-        """field()'s type, dtype and shape rules without its finiteness scan (apply's arguments)."""
+    def _host_array(self, a, name: str, writable: bool = False, apply_hint: bool = True) -> np.ndarray:
+        """field()'s type, dtype and shape rules without its finiteness scan (apply's arguments, whose refusal of
+        a device tensor points to Session.apply)."""
         if hasattr(a, "numpy") and hasattr(a, "device"):  # a torch tensor
             if a.device.type != "cpu":
-                raise ValueError(f"{name}: device tensors are not supported, pass a NumPy array or a CPU tensor "
-                                 "(Session.apply takes device tensors)")
+                raise ValueError(f"{name}: device tensors are not supported, pass a NumPy array or a CPU tensor"
+                                 + (" (Session.apply takes device tensors)" if apply_hint else ""))
             a = a.detach().numpy()
         if not isinstance(a, np.ndarray):
             raise ValueError(f"{name} must be a NumPy array or a CPU torch tensor")

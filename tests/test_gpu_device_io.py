@@ -269,6 +269,54 @@ def test_d7_validation(pkg, arg, ranks):
     assert s.solve(**{arg: good})["status"] == "converged"
 
 
+def test_d7_value_rules_on_the_device(pkg):
+    """One table of values through the three device checks (k_finite for rhs, k_reaction_check for a reaction
+    field, k_diffusion_check for a diffusion field): a NaN, +inf, -1.0, 0.0 and -0.0, each once at an interior
+    node and once on the box boundary of a [:, :N+1] view whose padding columns hold NaN.  Every call raises
+    ValueError exactly where the rule of its field -- written out here in NumPy -- is broken, succeeds
+    otherwise, and leaves a live session solving to the count it had."""
+    M, N = 24, 20
+    p = pkg.PoissonEllipse(M=M, N=N)
+    rules = {
+        "rhs": lambda a: np.isfinite(a).all(),
+        "reaction": lambda a: np.isfinite(a[1:-1, 1:-1]).all() and (a[1:-1, 1:-1] >= 0).all(),
+        "diffusion": lambda a: np.isfinite(a).all() and (a > 0).all(),
+    }
+    i, j = np.meshgrid(np.arange(M + 1), np.arange(N + 1), indexing="ij")
+    clean = 1.0 + 0.5 * np.sin(0.3 * i) * np.cos(0.2 * j)
+    plain = pkg.make_session(p)
+    count = plain.solve()["iters"]
+
+    def call(name, view):
+        if name == "rhs":
+            plain.init(rhs=view)
+        else:
+            assert pkg.make_session(p, **{name: view}).solve()["status"] == "converged"
+
+    cases = [("clean", None, None)]
+    for v in (np.nan, np.inf, -1.0, 0.0, -0.0):
+        cases += [(f"{v!r} interior", (11, 7), v), (f"{v!r} boundary", (M, 5), v), (f"{v!r} corner", (0, 0), v)]
+    refused = {name: 0 for name in rules}
+    for label, at, v in cases:
+        host = clean.copy()
+        if at is not None:
+            host[at] = v
+        wide = torch.full((M + 1, N + 5), float("nan"), dtype=torch.float64, device=DEV)
+        wide[:, :N + 1] = torch.from_numpy(host)
+        view = wide[:, :N + 1]
+        assert not view.is_contiguous()
+        for name, ok in rules.items():
+            if ok(host):
+                call(name, view)
+            else:
+                with pytest.raises(ValueError, match=name):
+                    call(name, view)
+                refused[name] += 1
+            assert plain.solve()["iters"] == count, (label, name)
+    # interior: all five break diffusion, NaN / inf / -1 reaction, NaN / inf rhs; the boundary: none breaks reaction
+    assert refused == {"rhs": 6, "reaction": 3, "diffusion": 15}
+
+
 @pytest.mark.parametrize("arg", ["rhs", "w0"])
 def test_d7_tensor_of_another_device(pkg, arg):
     if torch.cuda.device_count() < 2:
