@@ -429,57 +429,65 @@ PYBIND11_MODULE(_pmx, m) {
   // rhs / w0: optional (M+1) x (N+1) float64 arrays, see pmx/cpu_pcg.hpp
   // reaction: optional (M+1) x (N+1) float64 field c >= 0 (interior nodes; the boundary is not read)
   // diffusion: optional (M+1) x (N+1) float64 field k > 0 on every node (the box boundary included)
+  // domain: optional (M+1) x (N+1) float64 field phi of nodal level-set values, finite on every node: D = {phi < 0}
   m.def("cpu_solve", [](const ProblemSpec& s, int threads, bool keep, py::object rhs, py::object w0,
-                        py::object reaction, py::object diffusion) {
+                        py::object reaction, py::object diffusion, py::object domain) {
           s.validate();
           const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
           const FieldArg c = field_arg(reaction, s, "reaction", FieldRule::kNonNegInterior),
-                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive);
+                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive),
+                         ph = field_arg(domain, s, "domain");
           SolveResult r;
-          { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep, f.ptr, w.ptr, c.ptr, kf.ptr); }
+          { py::gil_scoped_release nogil; r = cpu_solve(s, threads, keep, f.ptr, w.ptr, c.ptr, kf.ptr, ph.ptr); }
           return result_dict(r, s, keep);
         }, py::arg("spec"), py::arg("threads") = 1, py::arg("keep_solution") = true,
         py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("reaction") = py::none(),
-        py::arg("diffusion") = py::none());
+        py::arg("diffusion") = py::none(), py::arg("domain") = py::none());
   m.def("cpu_solve_decomposed", [](const ProblemSpec& s, int nranks, Split split, int threads, bool keep,
-                                   py::object rhs, py::object w0, py::object reaction, py::object diffusion) {
+                                   py::object rhs, py::object w0, py::object reaction, py::object diffusion,
+                                   py::object domain) {
           s.validate();
           const FieldArg f = field_arg(rhs, s, "rhs"), w = field_arg(w0, s, "w0");
           const FieldArg c = field_arg(reaction, s, "reaction", FieldRule::kNonNegInterior),
-                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive);
+                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive),
+                         ph = field_arg(domain, s, "domain");
           SolveResult r;
           {
             py::gil_scoped_release nogil;
-            r = cpu_solve_decomposed(s, nranks, split, threads, keep, f.ptr, w.ptr, c.ptr, kf.ptr);
+            r = cpu_solve_decomposed(s, nranks, split, threads, keep, f.ptr, w.ptr, c.ptr, kf.ptr, ph.ptr);
           }
           return result_dict(r, s, keep);
         }, py::arg("spec"), py::arg("nranks"), py::arg("split") = Split::kReference,
         py::arg("threads") = 1, py::arg("keep_solution") = true, py::arg("rhs") = py::none(),
-        py::arg("w0") = py::none(), py::arg("reaction") = py::none(), py::arg("diffusion") = py::none());
+        py::arg("w0") = py::none(), py::arg("reaction") = py::none(), py::arg("diffusion") = py::none(),
+        py::arg("domain") = py::none());
   // x, y: C-contiguous (M+1) x (N+1) float64 arrays, validated by the caller (PoissonEllipse.apply); no
   // finiteness scan -- a NaN of x propagates to the nodes whose stencil reads it
   m.def("cpu_apply", [](const ProblemSpec& s, py::array_t<double, py::array::c_style> x, py::object y, double alpha,
-                        double beta, double gamma, double c0, py::object reaction, py::object diffusion) {
+                        double beta, double gamma, double c0, py::object reaction, py::object diffusion,
+                        py::object domain) {
           s.validate();
           const FieldArg c = field_arg(reaction, s, "reaction", FieldRule::kNonNegInterior),
-                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive);
+                         kf = field_arg(diffusion, s, "diffusion", FieldRule::kPositive),
+                         ph = field_arg(domain, s, "domain");
           auto fits = [&](const py::array& a) { return a.ndim() == 2 && a.shape(0) == s.M + 1 && a.shape(1) == s.N + 1; };
           py::array_t<double, py::array::c_style> ya;
           if (!y.is_none()) ya = y.cast<py::array_t<double, py::array::c_style>>();
           if (!fits(x) || (!y.is_none() && !fits(ya))) throw py::value_error("x and y must have shape (M+1, N+1)");
           const double *xp = x.data(), *yp = y.is_none() ? nullptr : ya.data();
           std::vector<double> r;
-          { py::gil_scoped_release nogil; r = cpu_apply(s, xp, yp, alpha, beta, gamma, c0, c.ptr, kf.ptr); }
+          { py::gil_scoped_release nogil; r = cpu_apply(s, xp, yp, alpha, beta, gamma, c0, c.ptr, kf.ptr, ph.ptr); }
           return to_numpy(r, {s.M + 1, s.N + 1});
         }, py::arg("spec"), py::arg("x"), py::arg("y") = py::none(), py::arg("alpha") = 1.0, py::arg("beta") = 0.0,
         py::arg("gamma") = 1.0, py::arg("const") = 0.0, py::arg("reaction") = py::none(),
-        py::arg("diffusion") = py::none());
-  m.def("cpu_assemble", [](const ProblemSpec& s) {
+        py::arg("diffusion") = py::none(), py::arg("domain") = py::none());
+  m.def("cpu_assemble", [](const ProblemSpec& s, py::object domain) {
+    const FieldArg ph = field_arg(domain, s, "domain");
     std::vector<double> a, b, B;
-    cpu_assemble(s, a, b, B);
+    cpu_assemble(s, a, b, B, ph.ptr);
     return py::make_tuple(to_numpy(a, {s.M + 2, s.N + 2}), to_numpy(b, {s.M + 2, s.N + 2}),
                           to_numpy(B, {s.M + 1, s.N + 1}));
-  });
+  }, py::arg("spec"), py::arg("domain") = py::none());
 
   // ---- GPU ----
   m.def("device_count", []() {
@@ -590,11 +598,12 @@ PYBIND11_MODULE(_pmx, m) {
   // The MemoryPlan of one subdomain of a pcg1 session (tests of the layout): sizes, and the byte offsets of
   // local (0, 0) of every field from the start of the fields; reaction: with the shift field
   // diffusion: with the shift field and the two face-coefficient fields (diff_field: at()'s indices of ak, bk;
-  // diff_extra: the bytes of ak's extra row behind the last field)
+  // diff_extra: the bytes of ak's extra row behind the last field); domain: a diffusion plan with the mask
   m.def("memory_plan", [](const ProblemSpec& s, int world, Split split, int rank, const std::string& dtype,
-                          bool reaction, bool diffusion) {
+                          bool reaction, bool diffusion, bool domain) {
     const Subdomain sd = decompose_2d(s.M, s.N, make_process_grid(world, s.M, s.N, split), rank);
-    const MemoryPlan p(s, sd, dtype == "fp64" ? DType::kFp64 : DType::kFp32, 1, 2, reaction, diffusion);
+    const MemoryPlan p(s, sd, dtype == "fp64" ? DType::kFp64 : DType::kFp32, 1, 2, reaction, diffusion || domain,
+                       domain);
     py::dict d;
     d["elem"] = p.elem; d["pitch"] = p.pitch; d["gh"] = p.gh; d["nx"] = sd.nx; d["ny"] = sd.ny;
     d["field_bytes"] = p.field_bytes; d["nfields"] = p.nfields; d["shift_field"] = p.shift_field();
@@ -602,13 +611,15 @@ PYBIND11_MODULE(_pmx, m) {
     py::list at;
     for (int f = 0; f < p.nfields + p.nshift + p.ndiff; ++f) at.append(p.at(f));
     d["at"] = at;
-    if (diffusion) {
+    if (domain) { d["mask_bytes"] = p.mask_bytes; d["mask_off"] = p.mask_off(); }
+    if (diffusion || domain) {
       d["ndiff"] = p.ndiff; d["diff_extra"] = p.diff_extra;
       d["diff_field"] = py::make_tuple(p.diff_field(0), p.diff_field(1));
     }
     return d;
   }, py::arg("spec"), py::arg("world") = 1, py::arg("split") = Split::kReference, py::arg("rank") = 0,
-     py::arg("dtype") = "fp64", py::arg("reaction") = false, py::arg("diffusion") = false);
+     py::arg("dtype") = "fp64", py::arg("reaction") = false, py::arg("diffusion") = false,
+     py::arg("domain") = false);
 
   py::class_<OpContext>(m, "OpContext", py::module_local())
       .def(py::init<const ProblemSpec&, int, int, int, int64_t, int>(), py::arg("spec"),
@@ -691,7 +702,8 @@ PYBIND11_MODULE(_pmx, m) {
                        bool rccl_graph, bool overlap, int vec_b, int waves_b, int tile_rows_b,
                        bool poison_halos, bool b_ring, int algo, bool defer_connect, int threaded,
                        int placement, double placement_budget_s, double placement_keep_free, int sharing,
-                       int block_tiles, int ca_s, int split_sweep, py::object reaction, py::object diffusion) {
+                       int block_tiles, int ca_s, int split_sweep, py::object reaction, py::object diffusion,
+                       py::object domain) {
              SessionConfig c;
              s.validate();
              // type, dtype, shape, stride and device of the field (and a host field's values) before anything
@@ -699,8 +711,10 @@ PYBIND11_MODULE(_pmx, m) {
              const int dev0 = devices.empty() ? device : devices[0];
              const SessionField rf = session_field(reaction, s, dev0, "reaction", FieldRule::kNonNegInterior);
              const SessionField df = session_field(diffusion, s, dev0, "diffusion", FieldRule::kPositive);
+             const SessionField pf = session_field(domain, s, dev0, "domain");
              c.reaction = rf.f;
              c.diffusion = df.f;
+             c.domain = pf.f;
              c.sharing = sharing;
              c.spec = s;
              c.opt = make_options(device, kernel, block, vec, waves, tile_rows, dtype, exact,
@@ -737,7 +751,21 @@ PYBIND11_MODULE(_pmx, m) {
            py::arg("threaded") = -1, py::arg("placement") = 0, py::arg("placement_budget_s") = 0.5,
            py::arg("placement_keep_free") = 0.5, py::arg("sharing") = 0, py::arg("block_tiles") = -1,
            py::arg("ca_s") = 3, py::arg("split_sweep") = -1, py::arg("reaction") = py::none(),
-           py::arg("diffusion") = py::none())
+           py::arg("diffusion") = py::none(), py::arg("domain") = py::none())
+      .def("set_domain", [](Session& s, py::object domain, py::object diffusion) {
+             if (domain.is_none()) throw py::value_error("domain must be an (M+1) x (N+1) float64 field");
+             const ProblemSpec& sp = s.solver(0).spec();
+             const int dev = s.solver(0).device();
+             const SessionField pf = session_field(domain, sp, dev, "domain");
+             const SessionField df = session_field(diffusion, sp, dev, "diffusion", FieldRule::kPositive);
+             py::gil_scoped_release g;
+             s.set_domain(pf.f, df.f);
+           }, py::arg("domain"), py::arg("diffusion") = py::none(),
+           "replace the level-set field phi of a session built with one (make_session(p, domain=phi)) and, with "
+           "it, the diffusion field (None: k = 1): the same types and checks as there (phi finite on every node, "
+           "ValueError before the session is touched).  The face-coefficient fields and the right-hand-side mask "
+           "are rewritten in place, so captured graphs stay valid; step() raises until the next init() / solve()")
+      .def_property_readonly("has_domain", &Session::has_domain)
       .def("set_diffusion", [](Session& s, py::object diffusion) { replace_field(s, diffusion, true); },
            py::arg("diffusion"),
            "replace the diffusion field k of a session built with one (make_session(p, diffusion=k)): the same "

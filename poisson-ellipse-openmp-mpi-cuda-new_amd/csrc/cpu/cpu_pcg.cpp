@@ -53,10 +53,35 @@ void scale_faces(std::vector<double>& a, std::vector<double>& b, int P, int gi0,
     }
 }
 
+// The geometric face coefficients of a local array of pitch P whose (0, 0) is global (gi0, gj0), rows 0 .. rows-1,
+// columns 0 .. cols-1, before scale_faces: the ellipse's (coef_a / coef_b, ghosts included, computed analytically and
+// never communicated), or with a level-set field phi those of D = {phi < 0} (geometry.hpp; faces the interior
+// stencils do not read get 1) -- the ellipse then plays no part.
+void fill_faces(std::vector<double>& a, std::vector<double>& b, int P, int gi0, int gj0, int rows, int cols,
+                const ProblemSpec& spec, const GridInfo& g, const geo::FaceTables& t, const double* phi) {
+  for (int li = 0; li < rows; ++li)
+    for (int lj = 0; lj < cols; ++lj) {
+      const size_t c = size_t(li) * P + lj;
+      const int gi = gi0 + li, gj = gj0 + lj;
+      if (phi) {
+        a[c] = geo::ls_coef_a(phi, spec.N + 1, spec.M, spec.N, g.eps, gi, gj);
+        b[c] = geo::ls_coef_b(phi, spec.N + 1, spec.M, spec.N, g.eps, gi, gj);
+      } else {
+        a[c] = geo::coef_a(t, g, gi, gj);
+        b[c] = geo::coef_b(t, g, gi, gj);
+      }
+    }
+}
+
+// the right-hand-side mask of interior node (i, j): phi < 0 with a domain, else the ellipse
+inline bool in_domain(const geo::FaceTables& t, const ProblemSpec& s, const double* phi, int i, int j) {
+  return phi ? geo::ls_inside(phi, s.N + 1, i, j) : geo::rhs_mask(t, s, i, j);
+}
+
 }  // namespace
 
 void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<double>& b,
-                  std::vector<double>& B) {
+                  std::vector<double>& B, const double* domain) {
   spec.validate();
   const GridInfo g(spec);
   const geo::FaceTables t(spec, g);
@@ -64,17 +89,13 @@ void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<d
   a.assign(size_t(M + 2) * pa, 0.0);
   b.assign(size_t(M + 2) * pa, 0.0);
   B.assign(size_t(M + 1) * pB, 0.0);
-  for (int i = 0; i <= M + 1; ++i)
-    for (int j = 0; j <= N + 1; ++j) {
-      a[size_t(i) * pa + j] = geo::coef_a(t, g, i, j);
-      b[size_t(i) * pa + j] = geo::coef_b(t, g, i, j);
-    }
+  fill_faces(a, b, pa, 0, 0, M + 2, N + 2, spec, g, t, domain);
   for (int i = 1; i <= M - 1; ++i)
-    for (int j = 1; j <= N - 1; ++j) B[size_t(i) * pB + j] = geo::rhs(t, spec, i, j);
+    for (int j = 1; j <= N - 1; ++j) B[size_t(i) * pB + j] = in_domain(t, spec, domain, i, j) ? spec.F : 0.0;
 }
 
 SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, const double* rhs,
-                      const double* w0, const double* reaction, const double* diffusion) {
+                      const double* w0, const double* reaction, const double* diffusion, const double* domain) {
   spec.validate();
   const GridInfo g(spec);
   const geo::FaceTables t(spec, g);
@@ -98,16 +119,12 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
 
   std::vector<double> a(n), b(n), w(n, 0.0), r(n, 0.0), z(n, 0.0), p(n, 0.0), Ap(n, 0.0),
       wprev(n, 0.0);
-  for (int i = 0; i <= M + 1; ++i)
-    for (int j = 0; j <= N + 1; ++j) {
-      a[size_t(i) * P + j] = geo::coef_a(t, g, i, j);
-      b[size_t(i) * P + j] = geo::coef_b(t, g, i, j);
-    }
+  fill_faces(a, b, P, 0, 0, M + 2, N + 2, spec, g, t, domain);
   if (diffusion) scale_faces(a, b, P, 0, 0, M + 2, N + 2, spec, diffusion);
   for (int i = 1; i <= M - 1; ++i)
     for (int j = 1; j <= N - 1; ++j) {
       const size_t g = size_t(i) * (N + 1) + j;
-      r[size_t(i) * P + j] = !rhs ? geo::rhs(t, spec, i, j) : geo::rhs_mask(t, spec, i, j) ? rhs[g] : 0.0;
+      r[size_t(i) * P + j] = !in_domain(t, spec, domain, i, j) ? 0.0 : rhs ? rhs[g] : spec.F;
       if (w0) w[size_t(i) * P + j] = w0[g];
     }
 
@@ -212,7 +229,8 @@ SolveResult cpu_solve(const ProblemSpec& spec, int threads, bool keep_solution, 
 }
 
 std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const double* y, double alpha, double beta,
-                              double gamma, double c0, const double* reaction, const double* diffusion) {
+                              double gamma, double c0, const double* reaction, const double* diffusion,
+                              const double* domain) {
   spec.validate();
   const GridInfo g(spec);
   const geo::FaceTables t(spec, g);
@@ -221,11 +239,7 @@ std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const do
   const size_t n = size_t(M + 2) * P;
   const double h1 = g.h1, h2 = g.h2, sigma = spec.sigma;
   std::vector<double> a(n), b(n), p(n, 0.0), out(size_t(M + 1) * Q, 0.0);
-  for (int i = 0; i <= M + 1; ++i)
-    for (int j = 0; j <= N + 1; ++j) {
-      a[size_t(i) * P + j] = geo::coef_a(t, g, i, j);
-      b[size_t(i) * P + j] = geo::coef_b(t, g, i, j);
-    }
+  fill_faces(a, b, P, 0, 0, M + 2, N + 2, spec, g, t, domain);
   if (diffusion) scale_faces(a, b, P, 0, 0, M + 2, N + 2, spec, diffusion);
   for (int i = 1; i <= M - 1; ++i)
     for (int j = 1; j <= N - 1; ++j) p[size_t(i) * P + j] = x[size_t(i) * Q + j];
@@ -254,7 +268,8 @@ std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const do
 // ---------------------------------------------------------------------------
 
 CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads, const double* rhs,
-                           const double* w0, const double* reaction, const double* diffusion)
+                           const double* w0, const double* reaction, const double* diffusion,
+                           const double* domain)
     : spec_(spec), g_(spec), sd_(sd), threads_(threads < 1 ? 1 : threads) {
   const geo::FaceTables t(spec, g_);
   const int nx = sd.nx, ny = sd.ny, P = ny + 2;
@@ -263,18 +278,14 @@ CpuSubdomain::CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int thr
   w_.assign(n, 0.0); r_.assign(n, 0.0); z_.assign(n, 0.0); p_.assign(n, 0.0); Ap_.assign(n, 0.0);
   // coefficients include the 1-cell halo, computed analytically (never communicated),
   // exactly like fic_reg_local (stage2-mpi/poisson_mpi_decomp.cpp:132-133)
-  for (int li = 0; li <= nx + 1; ++li)
-    for (int lj = 0; lj <= ny + 1; ++lj) {
-      const int gi = sd.gi0() + li, gj = sd.gj0() + lj;
-      a_[size_t(li) * P + lj] = geo::coef_a(t, g_, gi, gj);
-      b_[size_t(li) * P + lj] = geo::coef_b(t, g_, gi, gj);
-    }
+  fill_faces(a_, b_, P, sd.gi0(), sd.gj0(), nx + 2, ny + 2, spec, g_, t, domain);
   if (diffusion) scale_faces(a_, b_, P, sd.gi0(), sd.gj0(), nx + 2, ny + 2, spec, diffusion);
   for (int li = 1; li <= nx; ++li)
     for (int lj = 1; lj <= ny; ++lj) {
       const int gi = sd.gi0() + li, gj = sd.gj0() + lj;
-      B_[size_t(li) * P + lj] = !rhs ? geo::rhs(t, spec, gi, gj)
-                                : geo::rhs_mask(t, spec, gi, gj) ? rhs[size_t(gi) * (spec.N + 1) + gj] : 0.0;
+      B_[size_t(li) * P + lj] = !in_domain(t, spec, domain, gi, gj) ? 0.0
+                                : rhs                              ? rhs[size_t(gi) * (spec.N + 1) + gj]
+                                                                   : spec.F;
     }
   if (reaction) {
     sh_.assign(n, 0.0);
@@ -485,13 +496,15 @@ SolveResult cpu_pcg_loop(const ProblemSpec& spec, std::vector<CpuSubdomain*>& lo
 
 SolveResult cpu_solve_decomposed(const ProblemSpec& spec, int nranks, Split split,
                                  int threads_per_rank, bool keep_solution, const double* rhs,
-                                 const double* w0, const double* reaction, const double* diffusion) {
+                                 const double* w0, const double* reaction, const double* diffusion,
+                                 const double* domain) {
   spec.validate();
   const ProcGrid pg = make_process_grid(nranks, spec.M, spec.N, split);
   std::vector<CpuSubdomain> subs;
   subs.reserve(nranks);
   for (int r = 0; r < nranks; ++r)
-    subs.emplace_back(spec, decompose_2d(spec.M, spec.N, pg, r), threads_per_rank, rhs, w0, reaction, diffusion);
+    subs.emplace_back(spec, decompose_2d(spec.M, spec.N, pg, r), threads_per_rank, rhs, w0, reaction, diffusion,
+                      domain);
   std::vector<CpuSubdomain*> local;
   for (auto& s : subs) local.push_back(&s);
 

@@ -216,7 +216,8 @@ void apply_sigma_rules(const ProblemSpec& spec, const ProcGrid& grid, GpuOptions
   PMX_CHECK(o.resolved, "apply_sigma_rules needs resolve_options()");
   if (spec.sigma == 0.0 && !o.shift_field) return;
   auto refuse = [&](const char* option) {
-    throw std::invalid_argument(std::string(o.diffusion     ? "a diffusion field"
+    throw std::invalid_argument(std::string(o.domain        ? "a level-set domain"
+                                            : o.diffusion   ? "a diffusion field"
                                             : o.shift_field ? "a reaction field"
                                                             : "sigma != 0 (the screened problem)") +
                                 " runs pcg1 on the row march only: " + option + " is not built for it");
@@ -340,13 +341,15 @@ void GpuSubdomainSolver::construct(uintptr_t external_arena) {
   PMX_CHECK(!pcg1_ || (!opt.exact && (sd.grid.size() == 1 || (sd.nx >= 2 && sd.ny >= 2))),
             "pcg1 needs the fast arithmetic and a subdomain of at least 2 x 2 nodes");
   PMX_CHECK(!opt_.diffusion || (pcg1_ && opt_.shift_field), "a diffusion field runs pcg1 with the shift field");
-  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh, opt_.shift_field != 0, opt_.diffusion != 0);
+  PMX_CHECK(!opt_.domain || opt_.diffusion, "a level-set domain runs the diffusion sweeps");
+  plan_ = MemoryPlan(spec, sd, opt.dtype, opt_.algo, gh, opt_.shift_field != 0, opt_.diffusion != 0,
+                     opt_.domain != 0);
   const int elem = int(plan_.elem);
   geom_ = make_dev_geom(spec, sd, plan_.pitch);
   const DevGeom& G = geom_;
   {  // fail with a sizing message instead of a bare hipErrorOutOfMemory
     const size_t need = estimate_device_bytes_algo(spec, sd, opt.dtype, opt_.algo) +
-                        (plan_.nshift + plan_.ndiff) * plan_.field_bytes + plan_.diff_extra;
+                        (plan_.nshift + plan_.ndiff) * plan_.field_bytes + plan_.diff_extra + plan_.mask_bytes;
     PMX_CHECK(need <= free_b,
               "subdomain " << sd.nx << "x" << sd.ny << " (" << (ca_ ? "s-step, 7" : pcg1_ ? "pcg1, 5" : "pcg2, 4")
                            << " fields) needs " << need / 1e9 << " GB on device " << opt.device
@@ -732,6 +735,20 @@ void GpuSubdomainSolver::set_diffusion(const double* k, int64_t ld, hipStream_t 
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
+void GpuSubdomainSolver::set_domain(const double* phi, int64_t ldp, const double* k, int64_t ld, hipStream_t s) {
+  PMX_CHECK(has_domain(), "set_domain needs a solver built with a level-set domain (GpuOptions::domain)");
+  PMX_CHECK(phi && ldp >= spec_.N + 1 && (!k || ld >= spec_.N + 1),
+            "set_domain needs (M+1) x (N+1) device arrays with row stride >= N+1");
+  HIP_CHECK(hipSetDevice(opt_.device));
+  with_storage([&](auto t) {
+    using T = decltype(t);
+    launch_domain_fields<T>(geom_, phi, ldp, k, ld, reinterpret_cast<T*>(field_ptr(plan_.diff_field(0))),
+                            reinterpret_cast<T*>(field_ptr(plan_.diff_field(1))),
+                            reinterpret_cast<unsigned char*>(fields_.get() + plan_.mask_off()), s);
+  });
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
 void GpuSubdomainSolver::set_init_data_device(const double* f, const double* w0, int64_t ld_f, int64_t ld_w0) {
   PMX_CHECK(!f || ld_f >= sd_.ny, "row stride of the device right-hand side below the block's width");
   PMX_CHECK(!w0 || ld_w0 >= sd_.ny + 2, "row stride of the device initial guess below the block's width");
@@ -780,6 +797,7 @@ double GpuSubdomainSolver::residual_sumsq(const double* f, hipStream_t s, int64_
     X.cb = pw.a[1];
     X.npend = pw.n;
     set_operator(X, op<T>());
+    X.mask = mask_base();
     launch_init_data<T>(geom_, tables_, fields<T>().w, nullptr, HaloBufs<T>{}, part, init_tiles_, X, true, s);
   });
   HIP_CHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -923,6 +941,7 @@ void GpuSubdomainSolver::init_impl(hipStream_t s) {
     X.has_f = !stage_f_.empty() || dev_f_;
     X.has_w = !stage_w_.empty() || dev_w_;
     set_operator(X, op<T>());
+    X.mask = mask_base();
     X.rho_b = stop_ref_data_ ? 1 : 0;
     // the same cells from either source: a staged host copy, or the caller's device block through the
     // scatter kernel (set_init_data_device)

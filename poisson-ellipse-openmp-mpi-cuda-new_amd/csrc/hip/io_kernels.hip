@@ -6,6 +6,8 @@
 //   k_finite   raises a flag on any non-finite value of the whole array
 //   k_diffusion_check / k_face_fields   a diffusion field: the check of its values, and the two complete
 //              face-coefficient fields of a subdomain (geometry and k folded in) from the nodal values
+//   k_domain_fields   a level-set domain: the same two fields with the geometric factor from the nodal level-set
+//              values (geometry.hpp's ls_* functions), and the right-hand-side mask of the owned nodes
 //   k_gather   w of one subdomain, pending steps applied as GpuSubdomainSolver::download_w applies them,
 //              -> its block of the global array; global boundary nodes are written as zero
 //
@@ -18,6 +20,7 @@
 
 #include "pcg_device.hpp"
 #include "pmx/common.hpp"
+#include "pmx/geometry.hpp"
 #include "pmx/kernels.hpp"
 
 namespace pmx {
@@ -140,6 +143,33 @@ k_face_fields(DevGeom G, DevTables Tb, const double* __restrict__ k, int64_t ld,
   if (li <= G.nx + 2) bk[o] = static_cast<T>(b);
 }
 
+// k_face_fields for a level-set domain (launch_domain_fields): the same cells, the same order (0.5 (k' + k)) a and
+// the same single rounding; the geometric factor is geo::ls_coef_a / ls_coef_b of phi, the host's functions, which
+// return 1 for a face the interior stencils do not read and read phi on nodes of the box only.  k may be null
+// (k = 1).  The thread of an owned node also stores its byte of the right-hand-side mask, phi < 0.
+template <typename T>
+__global__ void __launch_bounds__(kIoCols)
+k_domain_fields(DevGeom G, const double* __restrict__ phi, int64_t ldp, const double* __restrict__ k, int64_t ld,
+                T* __restrict__ ak, T* __restrict__ bk, unsigned char* __restrict__ mask) {
+  const int lj = -1 + int(blockIdx.x * kIoCols + threadIdx.x);
+  const int li = -1 + int(blockIdx.y);
+  if (lj > int(G.pitch) - 2 || li > G.nx + 3) return;
+  const int gi = G.gi0 + li, gj = G.gj0 + lj;
+  const bool node = gi >= 0 && gi <= G.M && gj >= 0 && gj <= G.N;
+  double a = 1.0, b = 1.0;
+  if (node) {
+    auto kv = [&](int i, int j) { return k ? k[int64_t(i) * ld + j] : 1.0; };
+    const double kc = kv(gi, gj);
+    if (gi >= 1) a = (0.5 * (kv(gi - 1, gj) + kc)) * geo::ls_coef_a(phi, ldp, G.M, G.N, G.eps, gi, gj);
+    if (gj >= 1) b = (0.5 * (kv(gi, gj - 1) + kc)) * geo::ls_coef_b(phi, ldp, G.M, G.N, G.eps, gi, gj);
+  }
+  const int64_t o = int64_t(li) * G.pitch + lj;
+  ak[o] = static_cast<T>(a);
+  if (li <= G.nx + 2) bk[o] = static_cast<T>(b);
+  if (li >= 1 && li <= G.nx && lj >= 1 && lj <= G.ny)  // an owned node: an interior node of the box
+    mask[int64_t(li - 1) * G.pitch + lj] = geo::ls_inside(phi, ldp, gi, gj) ? 1 : 0;
+}
+
 // local nodes (li0 .. li0 + rows - 1) x (lj0 .. lj0 + cols - 1) of a subdomain whose local (0, 0) is
 // global (gi0, gj0); w, pa, pb point to local (0, 0)
 template <typename T>
@@ -209,6 +239,21 @@ template void launch_face_fields<double>(const DevGeom&, const DevTables&, const
                                          hipStream_t);
 template void launch_face_fields<float>(const DevGeom&, const DevTables&, const double*, int64_t, float*, float*,
                                         hipStream_t);
+
+template <typename T>
+void launch_domain_fields(const DevGeom& G, const double* phi, int64_t ldp, const double* k, int64_t ld, T* ak, T* bk,
+                          unsigned char* mask, hipStream_t s) {
+  PMX_CHECK(phi && ak && bk && mask && ldp >= G.N + 1 && (!k || ld >= G.N + 1),
+            "domain fields: need the level-set field (row stride >= N + 1), both outputs and the mask");
+  PMX_CHECK(G.nx + 5 <= 65535, "domain fields: too many rows for one launch: " << G.nx);
+  const dim3 grid(unsigned((G.pitch + kIoCols - 1) / kIoCols), unsigned(G.nx + 5));
+  hipLaunchKernelGGL((k_domain_fields<T>), grid, dim3(kIoCols), 0, s, G, phi, ldp, k, ld, ak, bk, mask);
+  HIP_CHECK(hipGetLastError());
+}
+template void launch_domain_fields<double>(const DevGeom&, const double*, int64_t, const double*, int64_t, double*,
+                                           double*, unsigned char*, hipStream_t);
+template void launch_domain_fields<float>(const DevGeom&, const double*, int64_t, const double*, int64_t, float*,
+                                          float*, unsigned char*, hipStream_t);
 
 template <typename T>
 void launch_gather(const T* w, const T* pa, double ca, const T* pb, double cb, int npend, int64_t pitch,

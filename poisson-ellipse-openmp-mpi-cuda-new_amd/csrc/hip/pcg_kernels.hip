@@ -59,7 +59,9 @@ TileCfg make_tiles(const DevGeom& G, int block, int rows) {
 // SH = 2 (a session with a reaction field): the node's own shift T(sigma + c) from X.shift -- the
 // subdomain's shift field, r's layout -- in place of X.sigma, in the same two places and in rho_B.
 // SH = 3 (a session with a diffusion field): as 2, and the four faces of the node come from the session's
-// face-coefficient fields X.ka / X.kb (ak(i), ak(i+1), bk(j), bk(j+1)) instead of the 1-D tables.
+// face-coefficient fields X.ka / X.kb (ak(i), ak(i+1), bk(j), bk(j+1)) instead of the 1-D tables.  With a
+// level-set domain such a session also holds X.mask, and the node is inside D iff its byte is set: a
+// wave-uniform run-time test in this instantiation alone.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double resid(double B, double Aw) {
   PMX_NO_CONTRACT
@@ -111,7 +113,13 @@ k_init(DevGeom G, DevTables Tb, T* __restrict__ w, T* __restrict__ r, HaloBufs<T
       [[maybe_unused]] double sg = X.sigma;
       if constexpr (SH >= 2) sg = double(X.shift[c]);
       // B_ij = F inside D (stage0/Withoutopenmp1.cpp:60)
-      const bool in = geo::inside(Tb.x[gi], yj, G.ax, G.by, G.ref_ellipse != 0);
+      bool in;
+      if constexpr (SH == 3) {
+        if (X.mask) in = X.mask[c - P] != 0;
+        else in = geo::inside(Tb.x[gi], yj, G.ax, G.by, G.ref_ellipse != 0);
+      } else {
+        in = geo::inside(Tb.x[gi], yj, G.ax, G.by, G.ref_ellipse != 0);
+      }
       T Bs;
       if constexpr (MODE == kInitPlain) {
         Bs = static_cast<T>(in ? G.F : 0.0);
@@ -305,6 +313,7 @@ void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> 
                  double* partials, const TileCfg& tc, hipStream_t s, const OperatorData<T>& op) {
   InitData<T> X;
   set_operator(X, op);
+  X.mask = op.mask;
   with_op_kind(op.kind(), [&](auto K) { PMX_BLOCK_DISPATCH(tc.block, PMX_K_INIT(B, kInitPlain, K)); });
   HIP_CHECK(hipGetLastError());
 }
@@ -318,7 +327,7 @@ template <typename T>
 void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
                       const TileCfg& tc, const InitData<T>& X, bool measure, hipStream_t s) {
   PMX_CHECK(tc.block == 256, "the data init runs the init tiling (256 columns per tile)");
-  with_op_kind(OperatorData<T>{X.sigma, X.shift, X.ka, X.kb}.kind(), [&](auto K) {
+  with_op_kind(OperatorData<T>{X.sigma, X.shift, X.ka, X.kb, X.mask}.kind(), [&](auto K) {
     if (measure) PMX_K_INIT(256, kInitMeasure, K);
     else PMX_K_INIT(256, kInitData, K);
   });

@@ -41,20 +41,23 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
   GpuOptions pre = cfg_.opt;
   // a multi-process RCCL run tracks device progress for its hang watchdog (GpuOptions::progress)
   if ((cfg_.comm == CommKind::kRccl || cfg_.comm == CommKind::kIpc) && cfg_.world > 1) pre.progress = 1;
-  const UserField &react = cfg_.reaction, &dif = cfg_.diffusion;
-  if (react || dif) {
+  const UserField &react = cfg_.reaction, &dif = cfg_.diffusion, &dom = cfg_.domain;
+  if (react || dif || dom) {
     if (cfg_.comm != CommKind::kSelf && cfg_.comm != CommKind::kLocal)
-      throw std::invalid_argument(std::string(react ? "a reaction field" : "a diffusion field") +
+      throw std::invalid_argument(std::string(react ? "a reaction field" : dif ? "a diffusion field"
+                                                                               : "a level-set domain") +
                                   " needs a session that owns every subdomain (world 1 or the local communicator); "
                                   "multi-process transports are not supported");
     pre.shift_field = 1;  // T(sigma + c), c = 0 without a reaction field
-    pre.diffusion = dif ? 1 : 0;
+    pre.diffusion = dif || dom ? 1 : 0;  // a domain session is a diffusion session, k = 1 without a field
+    pre.domain = dom ? 1 : 0;
   }
   GpuOptions base = resolve_options(pre);
   // sigma != 0 or a reaction field: pcg1 on the row march, or std::invalid_argument
   apply_sigma_rules(cfg_.spec, pg_, base);
-  if (react) check_coefficient(react, false);  // before anything is allocated
-  if (dif) check_coefficient(dif, true);
+  if (react) check_coefficient(react, FieldRule::kNonNegInterior, "reaction");  // before anything is allocated
+  if (dif) check_coefficient(dif, FieldRule::kPositive, "diffusion");
+  if (dom) check_coefficient(dom, FieldRule::kFinite, "domain");
   if (base.algo == -1) {
     HIP_CHECK(hipSetDevice(cfg_.devices[0]));
     size_t free_b = 0, total_b = 0;
@@ -73,12 +76,13 @@ Session::Session(const SessionConfig& cfg) : cfg_(cfg) {
     solvers_.push_back(std::make_unique<GpuSubdomainSolver>(cfg_.spec, sd, o));
   }
   if (react) upload_reaction(react);
-  if (dif) {
+  if (dif || dom) {
     if (!react) {  // the shift field of a diffusion session without a reaction field: T(sigma)
       const std::vector<double> zero(size_t(cfg_.spec.M + 1) * size_t(cfg_.spec.N + 1), 0.0);
       upload_reaction(UserField(zero.data()));
     }
-    upload_diffusion(dif);
+    if (dom) upload_domain(dom, dif);
+    else upload_diffusion(dif);
   }
   if (!cfg_.defer_connect) connect();
 }
@@ -234,15 +238,13 @@ void Session::check_values(std::initializer_list<FieldCheck> fields, int device,
   }
 }
 
-void Session::check_coefficient(const UserField& f, bool diffusion) const {
-  const std::string name = diffusion ? "diffusion" : "reaction";
+void Session::check_coefficient(const UserField& f, FieldRule rule, const std::string& name) const {
   if (f.stride(cfg_.spec.N) < cfg_.spec.N + 1) throw std::invalid_argument(name + ": row stride below N + 1");
   if (f.on_device)
     for (int d : cfg_.devices)
       if (d != cfg_.devices[0])
         throw std::invalid_argument("a device " + name + " field needs every subdomain of the session on its device");
-  check_values({{&f, diffusion ? FieldRule::kPositive : FieldRule::kNonNegInterior, name.c_str()}}, cfg_.devices[0],
-               f.stream);
+  check_values({{&f, rule, name.c_str()}}, cfg_.devices[0], f.stream);
 }
 
 void Session::upload_reaction(const UserField& c) {
@@ -269,14 +271,69 @@ void Session::upload_diffusion(const UserField& k) {
   }
 }
 
+namespace {
+
+// A global field for a setup kernel of device `device`: a device field as it is, a host field as a dense
+// temporary device copy that lives as long as the object.
+struct OnDevice {
+  DevPtr<double> tmp;
+  const double* ptr = nullptr;
+  int64_t ld = 0;
+  OnDevice(const UserField& f, int M, int N, int device) {
+    if (!f) return;
+    ld = f.stride(N);
+    ptr = f.ptr;
+    if (f.on_device) return;
+    HIP_CHECK(hipSetDevice(device));
+    double* raw = nullptr;
+    HIP_CHECK(hipMalloc(&raw, size_t(M + 1) * size_t(N + 1) * sizeof(double)));
+    tmp.reset(raw);
+    HIP_CHECK(hipMemcpy2D(raw, size_t(N + 1) * sizeof(double), f.ptr, size_t(ld) * sizeof(double),
+                          size_t(N + 1) * sizeof(double), size_t(M + 1), hipMemcpyHostToDevice));
+    ptr = raw;
+    ld = N + 1;
+  }
+};
+
+}  // namespace
+
+void Session::upload_domain(const UserField& phi, const UserField& k) {
+  const int M = cfg_.spec.M, N = cfg_.spec.N;
+  // the kernel runs on phi's stream (a host phi: the null stream, after the blocking copies); a device k of
+  // another stream has been consumed up to here by its value check, which waits for that stream
+  if (k && k.on_device && !(phi.on_device && phi.stream == k.stream)) HIP_CHECK(hipStreamSynchronize(k.stream));
+  for (auto& sp : solvers_) {
+    const OnDevice p(phi, M, N, sp->device()), q(k, M, N, sp->device());
+    sp->set_domain(p.ptr, p.ld, q.ptr, q.ld, phi.on_device ? phi.stream : nullptr);
+  }
+}
+
+void Session::set_domain(const UserField& phi, const UserField& k) {
+  if (!has_domain())
+    throw std::invalid_argument("set_domain needs a session built with a level-set domain (make_session(p, "
+                                "domain=phi)): sessions without one hold no right-hand-side mask");
+  if (!phi) throw std::invalid_argument("set_domain: no field given");
+  check_coefficient(phi, FieldRule::kFinite, "domain");
+  if (k) check_coefficient(k, FieldRule::kPositive, "diffusion");
+  if (!drivers_.empty()) synchronize();  // no sweep in flight reads the fields
+  upload_domain(phi, k);
+  cfg_.domain = phi;  // (kept as flags: has_domain / has_diffusion; the memory is the caller's)
+  cfg_.diffusion = k;
+  stale_ = true;
+}
+
 void Session::set_coefficient(const UserField& f, bool diffusion) {
   const std::string name = diffusion ? "diffusion" : "reaction";
+  if (diffusion && has_domain())
+    throw std::invalid_argument("set_diffusion: the session was built with a level-set domain, whose geometry is not "
+                                "retained, so the faces cannot be refolded from k alone; call set_domain(phi, "
+                                "diffusion=k)");
   if (!(diffusion ? has_diffusion() : has_reaction()))
     throw std::invalid_argument("set_" + name + " needs a session built with a " + name + " field (make_session(p, " +
                                 name + (diffusion ? "=k" : "=c") + ")): sessions without one hold no " +
                                 (diffusion ? "face-coefficient fields" : "shift field"));
   if (!f) throw std::invalid_argument("set_" + name + ": no field given");
-  check_coefficient(f, diffusion);
+  check_coefficient(f, diffusion ? FieldRule::kPositive : FieldRule::kNonNegInterior, name);
   if (!drivers_.empty()) synchronize();  // no sweep in flight reads the fields
   if (diffusion) upload_diffusion(f);
   else upload_reaction(f);
@@ -473,8 +530,8 @@ void Session::apply_device(const UserField& x, const UserField& out, const UserF
 }
 
 void Session::step(int64_t n) {
-  PMX_CHECK(!stale_, "step: the reaction or diffusion field changed (set_reaction / set_diffusion) since the last "
-                     "init; call init() or solve()");
+  PMX_CHECK(!stale_, "step: the reaction or diffusion field or the domain changed (set_reaction / set_diffusion / "
+                     "set_domain) since the last init; call init() or solve()");
   for_drivers([n](size_t, PcgDriver& d) { d.enqueue_iterations(n); });
 }
 
@@ -492,8 +549,8 @@ RunStats Session::solve_impl(int poll_batches, bool do_init, int64_t every, cons
   // identical everywhere); rank 0's statistics are returned
   std::vector<RunStats> st(drivers_.size());
   if (do_init) stale_ = false;
-  PMX_CHECK(!stale_, "the reaction or diffusion field changed (set_reaction / set_diffusion) since the last init; "
-                     "call init() or solve()");
+  PMX_CHECK(!stale_, "the reaction or diffusion field or the domain changed (set_reaction / set_diffusion / "
+                     "set_domain) since the last init; call init() or solve()");
   for_drivers([&](size_t i, PcgDriver& d) {
     std::function<void(const PcgState&)> cb;
     if (every > 0 && !save_path.empty()) {

@@ -42,32 +42,37 @@ struct SolveResult {
 // coefficients a[i,j] <- (0.5 (k[i-1,j] + k[i,j])) a[i,j], b[i,j] <- (0.5 (k[i,j-1] + k[i,j])) b[i,j] -- the
 // fictitious coefficient 1/eps included, so the medium outside D is k/eps -- and everything else the same
 // algebra on them.  k = 1 multiplies by exactly 1.0: the solve without the argument, bitwise.
+// domain: optional global field phi of nodal level-set values, finite on every node: D = {phi < 0} replaces the
+// ellipse.  The face coefficients are geo::ls_coef_a / ls_coef_b of phi (geometry.hpp: cell-centre means, one
+// linear crossing per face, theta + (1 - theta) / eps) and the right-hand-side mask is phi < 0 on the node;
+// diffusion scales those faces as it scales the ellipse's.
 SolveResult cpu_solve(const ProblemSpec& spec, int threads = 1, bool keep_solution = true,
                       const double* rhs = nullptr, const double* w0 = nullptr, const double* reaction = nullptr,
-                      const double* diffusion = nullptr);
+                      const double* diffusion = nullptr, const double* domain = nullptr);
 
 // Assemble the reference's 2D arrays on the host (tests: kernel bit-equality).
-// a, b are (M+2) x (N+2) including ghost nodes; B is (M+1) x (N+1).
+// a, b are (M+2) x (N+2) including ghost nodes; B is (M+1) x (N+1).  domain: as cpu_solve.
 void cpu_assemble(const ProblemSpec& spec, std::vector<double>& a, std::vector<double>& b,
-                  std::vector<double>& B);
+                  std::vector<double>& B, const double* domain = nullptr);
 
 // The operator itself, the host twin of Session::apply_device: alpha L x + beta x + gamma y + c0 on the interior
 // nodes and 0 on the box boundary of a global (M+1) x (N+1) row-major array, L = A + spec.sigma I -- the plain
 // matrix on the whole box, no ellipse mask -- in cpu_solve's mat_A arithmetic.  Boundary values of x count as 0
 // and are not read; y may be null (no y term).  Combination order: v = alpha Lx; v = fma(beta, x, v);
 // v = fma(gamma, y, v) with y; v += c0 -- and Lx itself for alpha = 1, beta = 0, no y, c0 = 0.
-// reaction, diffusion: as cpu_solve (L = A_k + (sigma + c) I).
+// reaction, diffusion, domain: as cpu_solve (L = A_k + (sigma + c) I, A_k on the faces of the domain).
 std::vector<double> cpu_apply(const ProblemSpec& spec, const double* x, const double* y = nullptr, double alpha = 1.0,
                               double beta = 0.0, double gamma = 1.0, double c0 = 0.0, const double* reaction = nullptr,
-                              const double* diffusion = nullptr);
+                              const double* diffusion = nullptr, const double* domain = nullptr);
 
 // One rank's block (local arrays (nx+2) x (ny+2), row-major, pitch ny+2).
 class CpuSubdomain {
  public:
-  // rhs / w0 / reaction / diffusion: as cpu_solve (global arrays; this block, and for w0 its ring, are copied;
-  // diffusion is folded into the block's face coefficients)
+  // rhs / w0 / reaction / diffusion / domain: as cpu_solve (global arrays; this block, and for w0 its ring, are
+  // copied; domain and diffusion are folded into the block's face coefficients and mask)
   CpuSubdomain(const ProblemSpec& spec, const Subdomain& sd, int threads, const double* rhs = nullptr,
-               const double* w0 = nullptr, const double* reaction = nullptr, const double* diffusion = nullptr);
+               const double* w0 = nullptr, const double* reaction = nullptr, const double* diffusion = nullptr,
+               const double* domain = nullptr);
 
   const Subdomain& sd() const { return sd_; }
   int pitch() const { return sd_.ny + 2; }
@@ -106,7 +111,8 @@ class CpuSubdomain {
 SolveResult cpu_solve_decomposed(const ProblemSpec& spec, int nranks, Split split,
                                  int threads_per_rank = 1, bool keep_solution = true,
                                  const double* rhs = nullptr, const double* w0 = nullptr,
-                                 const double* reaction = nullptr, const double* diffusion = nullptr);
+                                 const double* reaction = nullptr, const double* diffusion = nullptr,
+                                 const double* domain = nullptr);
 
 // Generic lock-step PCG over CpuSubdomains with pluggable collectives.  The MPI
 // app supplies MPI-backed callbacks; the in-process driver supplies local ones.

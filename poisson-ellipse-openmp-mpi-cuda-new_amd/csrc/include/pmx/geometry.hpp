@@ -20,6 +20,7 @@
 #pragma once
 
 #include <cmath>
+#include <cstdint>
 #include <limits>
 #include <vector>
 
@@ -95,6 +96,50 @@ PMX_HD inline bool inside(double x, double y, double ax, double by, bool referen
   const double u = x / ax, v = y / by;
   return u * u + v * v < 1.0;
 }
+
+// ---- level-set domains: D = {phi < 0}, phi an (M+1) x (N+1) field of nodal values (row stride ld) ----
+// The ellipse above is one shape; a session or a CPU solve built with `domain` takes its face coefficients
+// and its right-hand-side mask from phi through the functions below instead -- host and device run the same
+// fp64 operations in the same order, so both produce the same bits.
+
+// phi at the centre (x_i - h1/2, y_j - h2/2) of cell (i, j), i = 1..M, j = 1..N: the mean of its four nodes
+PMX_HD inline double ls_cell(const double* phi, int64_t ld, int i, int j) {
+  PMX_NO_CONTRACT
+  const double* p = phi + int64_t(i - 1) * ld + (j - 1);
+  return 0.25 * ((p[0] + p[1]) + (p[ld] + p[ld + 1]));
+}
+
+// Inside fraction of a face whose end values are p and q: one linear crossing per face, so a feature thinner
+// than a cell is not resolved.
+PMX_HD inline double ls_theta(double p, double q) {
+  PMX_NO_CONTRACT
+  const bool pn = p < 0.0, qn = q < 0.0;
+  if (pn && qn) return 1.0;
+  if (!pn && !qn) return 0.0;
+  const double n = pn ? p : q, m = pn ? q : p;  // n < 0 <= m
+  return n / (n - m);
+}
+
+// The face coefficient of an inside fraction: exactly 1 for theta = 1 and exactly 1/eps for theta = 0; no
+// snapping of nearly full or nearly empty faces (face_coef's 1e-9).
+PMX_HD inline double ls_coef(double theta, double eps) {
+  PMX_NO_CONTRACT
+  return theta + (1.0 - theta) / eps;
+}
+
+// a(i, j): the face between nodes (i-1, j) and (i, j), from cell centre (i, j) to (i, j+1); the faces the
+// interior stencils read are i = 1..M, j = 1..N-1.  Every other face gets 1.
+PMX_HD inline double ls_coef_a(const double* phi, int64_t ld, int M, int N, double eps, int i, int j) {
+  if (i < 1 || i > M || j < 1 || j > N - 1) return 1.0;
+  return ls_coef(ls_theta(ls_cell(phi, ld, i, j), ls_cell(phi, ld, i, j + 1)), eps);
+}
+// b(i, j): the face between nodes (i, j-1) and (i, j), from cell centre (i, j) to (i+1, j); i = 1..M-1, j = 1..N
+PMX_HD inline double ls_coef_b(const double* phi, int64_t ld, int M, int N, double eps, int i, int j) {
+  if (i < 1 || i > M - 1 || j < 1 || j > N) return 1.0;
+  return ls_coef(ls_theta(ls_cell(phi, ld, i, j), ls_cell(phi, ld, i + 1, j)), eps);
+}
+// the right-hand-side mask: interior node (i, j) is in D iff phi < 0 there
+PMX_HD inline bool ls_inside(const double* phi, int64_t ld, int i, int j) { return phi[int64_t(i) * ld + j] < 0.0; }
 
 // Analytic solution of -Δu = F in the ellipse, u = 0 on its boundary: used for
 // accuracy reports (the reference states (1-x^2-4y^2)/10 in its report but never

@@ -179,6 +179,10 @@ struct GpuOptions {
   // the field state of the shift switch, so `shift_field` is set with it -- and runs the diffusion sweeps, in
   // fp64 registers for either storage type.  Set by the Session; the values arrive through set_diffusion.
   int diffusion = 0;
+  // The session solves on a level-set domain D = {phi < 0} (Session's `domain`): a diffusion session (`diffusion`
+  // and `shift_field` are set with it) whose face-coefficient fields hold the domain's faces and which also keeps
+  // the right-hand-side mask (MemoryPlan::mask_bytes).  Set by the Session; the values arrive through set_domain.
+  int domain = 0;
   bool resolved = false;  // environment overrides already applied (resolve_options)
 };
 
@@ -311,6 +315,16 @@ class GpuSubdomainSolver {
   // and nothing is exchanged, as set_reaction.
   void set_diffusion(const double* k, int64_t ld, hipStream_t s);
   bool has_diffusion() const { return plan_.ndiff != 0; }
+  // Solvers built with GpuOptions::domain: (re)fill the face-coefficient fields and the right-hand-side mask from
+  // the nodal level-set values phi (device memory, row stride ldp) and the optional nodal diffusion field k (null:
+  // k = 1), by one kernel on s (launch_domain_fields: set_diffusion's cells).  Returns after s has consumed both;
+  // nothing of phi is retained.
+  void set_domain(const double* phi, int64_t ldp, const double* k, int64_t ld, hipStream_t s);
+  bool has_domain() const { return plan_.mask_bytes != 0; }
+  // the right-hand-side mask (MemoryPlan::mask_bytes' layout); nullptr without a domain
+  const unsigned char* mask_base() const {
+    return plan_.mask_bytes ? reinterpret_cast<const unsigned char*>(fields_.get() + plan_.mask_off()) : nullptr;
+  }
   // the face-coefficient fields (f: 0 ak, 1 bk) at local (0, 0) in the storage type; nullptr without
   const void* face_base(int f) const { return plan_.ndiff ? field_ptr(plan_.diff_field(f)) : nullptr; }
   // the shift field at local (0, 0) in the storage type; nullptr without a reaction field
@@ -318,7 +332,7 @@ class GpuSubdomainSolver {
   // the operator of this subdomain: sigma, and the fields above in the storage type T (void: type-erased)
   template <typename T> OperatorData<T> op() const {
     return {spec_.sigma, static_cast<const T*>(shift_base()), static_cast<const T*>(face_base(0)),
-            static_cast<const T*>(face_base(1))};
+            static_cast<const T*>(face_base(1)), mask_base()};
   }
   int64_t pitch() const { return plan_.pitch; }
   size_t elem_bytes() const { return plan_.elem; }

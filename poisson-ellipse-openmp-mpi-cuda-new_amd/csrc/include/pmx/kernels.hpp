@@ -86,7 +86,7 @@ enum AblBits : int {
 template <typename T>
 void launch_init(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H,
                  double* partials, const TileCfg& tc, hipStream_t s,
-                 const OperatorData<T>& op = {});  // op.kind() picks the kernel (as InitData's last four members)
+                 const OperatorData<T>& op = {});  // op.kind() picks the kernel (as InitData's operator members)
 
 // k_init with data (GpuSubdomainSolver::set_init_data / residual_norm), on launch_init's tiling.
 //   data init (measure = false): r holds f on the owned nodes (has_f; else the constant G.F), w holds
@@ -119,6 +119,11 @@ struct InitData {
   // them instead of forming them from the 1-D tables
   const T* ka = nullptr;
   const T* kb = nullptr;
+  // a session with a level-set domain (a diffusion session): its right-hand-side mask, one byte per owned node
+  // -- node (i, j) at mask[(i - 1) pitch + j], != 0 inside D -- read in place of the ellipse predicate by the
+  // diffusion kernels; null: the ellipse.  The last member: kernels built before it see their arguments where
+  // they were.
+  const unsigned char* mask = nullptr;
 };
 template <typename T>
 void launch_init_data(const DevGeom& G, const DevTables& Tb, T* w, T* r, HaloBufs<T> H, double* partials,
@@ -335,6 +340,14 @@ void launch_scatter_shift(const double* src, int64_t ld, T* dst, int64_t pitch, 
 // G.pitch; written: local rows -1 .. nx+3 of ak, -1 .. nx+2 of bk, columns -1 .. G.pitch-2 (the whole row).
 template <typename T>
 void launch_face_fields(const DevGeom& G, const DevTables& Tb, const double* k, int64_t ld, T* ak, T* bk, hipStream_t s);
+// A level-set domain (io_kernels.hip).  The same two fields, on the same cells, with the geometric factor from
+// the nodal level-set values phi (global (M+1) x (N+1), row stride ldp, device memory) instead of the tables --
+// geo::ls_coef_a / ls_coef_b, each cell reading its 2 x 3 and 3 x 2 nodes of the global array, across
+// subdomain borders -- and k optional (null: k = 1, the factor 0.5 (1 + 1) = 1 exactly).  mask (MemoryPlan::
+// mask_bytes' layout): byte (li - 1) pitch + lj <- phi < 0 at the node, on the owned nodes.
+template <typename T>
+void launch_domain_fields(const DevGeom& G, const double* phi, int64_t ldp, const double* k, int64_t ld, T* ak, T* bk,
+                          unsigned char* mask, hipStream_t s);
 // local nodes (li0 .. li0+rows-1) x (lj0 .. lj0+cols-1) of a subdomain with local (0, 0) at global
 // (gi0, gj0) -> out[gi * ld + gj]: w + ca pa (+ cb pb) as launch_error_norms forms it (w, pa, pb point to
 // local (0, 0), row stride pitch); nodes on the global boundary (gi in {0, M}, gj in {0, N}) get zero

@@ -34,12 +34,16 @@ struct MemoryPlan {
   // that row is diff_extra bytes behind the last field.  0 without: every other plan is what it was.
   int ndiff = 0;
   size_t diff_extra = 0;
+  // The right-hand-side mask of a session with a level-set domain: one byte per node on the owned rows
+  // 1 .. nx in the fields' pitch (node (li, lj) at byte (li - 1) pitch + lj), behind everything above.
+  // 0 without: every other plan is what it was.
+  size_t mask_bytes = 0;
 
   MemoryPlan() = default;
   // algo: 1 pcg1, 2 pcg2, 3 the s-step PCG (GpuOptions::algo); ghost_rows: 2, or the s-step's s / 2s on
   // decomposed grids -- rows, and columns on 2-D blocks
   MemoryPlan(const ProblemSpec& spec, const Subdomain& sd, DType dtype, int algo, int ghost_rows, bool shift = false,
-             bool diffusion = false)
+             bool diffusion = false, bool mask = false)
       : elem(dtype == DType::kFp64 ? 8 : 4), align(256 / elem), gh(ghost_rows), nfields(algo == 1 || algo == 3 ? 5 : 4),
         nshift(shift || diffusion ? 1 : 0), ndiff(diffusion ? 2 : 0) {
     const auto round_up = [](size_t x, size_t a) { return (x + a - 1) / a * a; };
@@ -59,11 +63,14 @@ struct MemoryPlan {
       face_bytes = round_up((31 + rows) * 8, 256);
     }
     if (ndiff) diff_extra = round_up(size_t(pitch) * elem, 256);
+    if (mask) mask_bytes = round_up(size_t(pitch) * size_t(sd.nx), 256);
     table_bytes = (4 * size_t(spec.M + 2) + 4 * size_t(spec.N + 2)) * sizeof(double) +
                   8 * size_t(spec.M + 2) * sizeof(int);
   }
 
-  size_t fields_total() const { return size_t(nfields + nshift + ndiff) * field_bytes + diff_extra; }
+  size_t fields_total() const { return mask_off() + mask_bytes; }
+  // byte offset of the mask (its row 1, column 0) from the start of the fields
+  size_t mask_off() const { return size_t(nfields + nshift + ndiff) * field_bytes + diff_extra; }
   int shift_field() const { return nshift ? nfields : -1; }  // at()'s index of the shift field, -1: none
   // at()'s index of a face-coefficient field (f: 0 ak, 1 bk), -1: none
   int diff_field(int f) const { return ndiff ? nfields + nshift + (f == 0 ? 1 : 0) : -1; }

@@ -18,13 +18,17 @@ constexpr bool pcg1_dif(OpKind k) { return k == OpKind::kDiffusion; }
 
 // What defines A + shift on one subdomain: ProblemSpec::sigma; the shift field T(sigma + c) of a session with a
 // reaction or a diffusion field; the face-coefficient fields ak, bk of a session with a diffusion field.  The
-// fields at local (0, 0), in the storage type T (void: type-erased, as ApplyCoef keeps them).
+// fields at local (0, 0), in the storage type T (void: type-erased, as ApplyCoef keeps them).  A session with a
+// level-set domain is a diffusion session (its face fields hold the domain's faces) that also keeps the
+// right-hand-side mask: one byte per owned node, MemoryPlan::mask_bytes' layout.  The mask is no part of the
+// operator -- only the inits read it.
 template <typename T>
 struct OperatorData {
   double sigma = 0.0;
   const T* shift = nullptr;
   const T* ka = nullptr;
   const T* kb = nullptr;
+  const unsigned char* mask = nullptr;
   OpKind kind() const {
     if (ka) {
       PMX_CHECK(shift && kb, "a diffusion session holds the shift field and both face fields");
@@ -35,7 +39,8 @@ struct OperatorData {
   }
 };
 
-// The four trailing members of a kernel argument struct (InitData<T>, ApplyCoef) from the descriptor.
+// The four operator members of a kernel argument struct (InitData<T>, ApplyCoef) from the descriptor.  The mask is
+// not among them: the inits copy it into InitData<T>::mask themselves.
 template <typename X, typename T>
 void set_operator(X& x, const OperatorData<T>& op) {
   x.sigma = op.sigma;
@@ -57,7 +62,7 @@ decltype(auto) with_op_kind(OpKind kind, F&& f) {
 
 // Value rules of a global (M+1) x (N+1) fp64 field: rhs and w0 are finite on every node; a reaction field is
 // finite and >= 0 on the interior nodes 1..M-1 x 1..N-1 (its box-boundary values are never read; -0.0 passes); a
-// diffusion field is finite and > 0 on every node.
+// diffusion field is finite and > 0 on every node; a level-set field (domain) is finite on every node.
 enum class FieldRule { kFinite, kNonNegInterior, kPositive };
 
 // "<name>" + this: the refusal of a field that breaks its rule

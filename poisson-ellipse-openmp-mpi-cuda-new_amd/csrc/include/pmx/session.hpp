@@ -67,6 +67,12 @@ struct SessionConfig {
   // (GpuSubdomainSolver::set_diffusion) and the shift field (filled with sigma when there is no reaction
   // field).  The rules and refusals of `reaction` apply.
   UserField diffusion;
+  // Level-set domain: phi(x, y), nodal values like `diffusion`, finite on every node; D = {phi < 0} replaces the
+  // ellipse in the face coefficients and in the right-hand-side mask (geometry.hpp: ls_coef_a / ls_coef_b /
+  // ls_inside).  The session is a diffusion session -- k = 1 without `diffusion` -- whose face-coefficient
+  // fields hold the domain's faces, plus one mask byte per owned node; phi itself is not retained.  The rules and
+  // refusals of `diffusion` apply.
+  UserField domain;
 };
 
 class Session {
@@ -126,6 +132,12 @@ class Session {
   // until the next init() / solve().
   void set_diffusion(const UserField& k);
   bool has_diffusion() const { return bool(cfg_.diffusion); }
+  // Replace the domain of a session built with one (SessionConfig::domain), and with it the diffusion field (k
+  // empty: k = 1): both checked before the session is touched, the face-coefficient fields and the mask rewritten
+  // in place, step() throws until the next init() / solve().  set_diffusion on such a session throws: the
+  // geometry is not retained, so the faces cannot be refolded from k alone.
+  void set_domain(const UserField& phi, const UserField& k);
+  bool has_domain() const { return bool(cfg_.domain); }
   void step(int64_t n);
   void synchronize();
   RunStats solve(int poll_batches = 1);
@@ -199,18 +211,23 @@ class Session {
   void check_values(std::initializer_list<FieldCheck> fields, int device, hipStream_t s) const;
   // the device fields among rhs and w0, on stream_of(0)
   void check_finite(const UserField& rhs, const UserField& w0);
-  // a reaction field (diffusion: a diffusion field) of the constructor or a set_*: its row stride, then its
-  // values -- a device field on its producer's stream, and only with every subdomain on its device
-  void check_coefficient(const UserField& f, bool diffusion) const;
+  // a reaction, diffusion or level-set field of the constructor or a set_*: its row stride, then its values
+  // under `rule` -- a device field on its producer's stream, and only with every subdomain on its device
+  void check_coefficient(const UserField& f, FieldRule rule, const std::string& name) const;
   // set_reaction / set_diffusion: the field checked, the session idle, the upload, the iteration state stale
   void set_coefficient(const UserField& f, bool diffusion);
   void upload_reaction(const UserField& c);
   // a host field goes up whole to a temporary device copy per subdomain, so that one kernel forms the face
   // fields from either source (the same bits)
   void upload_diffusion(const UserField& k);
+  // the same for a level-set domain: phi, and k where there is one (empty: k = 1)
+  void upload_domain(const UserField& phi, const UserField& k);
   // what the refusals call the session's coefficient field; nullptr without one
   const char* field_noun() const {
-    return has_diffusion() ? "a diffusion field" : has_reaction() ? "a reaction field" : nullptr;
+    return has_domain()      ? "a level-set domain"
+           : has_diffusion() ? "a diffusion field"
+           : has_reaction()  ? "a reaction field"
+                             : nullptr;
   }
   bool stale_ = false;  // set_reaction since the last init: the iteration state is the old operator's
 

@@ -116,12 +116,19 @@ class PoissonEllipse:
         c = self.F / (2.0 / self.ax ** 2 + 2.0 / self.by ** 2)
         return np.where(q > 0, c * q, 0.0)
 
-    def require_closed_form(self, what: str):
+    def require_closed_form(self, what: str, domain=None):
+        if domain is not None:
+            raise ValueError(f"{what}: the closed-form solution belongs to the ellipse, not to a level-set domain; "
+                             "pass the solution of your problem as exact=")
         if self.sigma != 0.0:
             raise ValueError(f"{what}: the closed-form solution holds for sigma = 0 only (sigma = {self.sigma}); "
                              "pass the solution of your problem as exact=")
 
-    def inside_mask(self):
+    def inside_mask(self, domain=None):
+        """The nodes of D as an (M+1)x(N+1) bool array: the ellipse, or phi < 0 for a level-set field `domain`
+        (domain_field()'s rules)."""
+        if domain is not None:
+            return self.domain_field(domain) < 0.0
         x, y = self.coords()
         X, Y = np.meshgrid(x, y, indexing="ij")
         if self.is_reference_ellipse():
@@ -176,6 +183,21 @@ class PoissonEllipse:
             raise ValueError(f"{name} must be finite and > 0 on every node")
         return np.ascontiguousarray(a)
 
+    def domain_field(self, phi, name: str = "domain") -> Optional[np.ndarray]:
+        """A level-set field phi(x, y) as a C-contiguous float64 (M+1)x(N+1) array, or None: field()'s rules --
+        type, dtype, shape, finite on every node.  D = {phi < 0}; see solve()."""
+        return self.field(phi, name)
+
+    def ellipse_levelset(self) -> np.ndarray:
+        """(x/ax)² + (y/by)² - 1 on the nodes (x² + 4y² - 1 for the reference ellipse): this problem's ellipse as
+        a level-set field.  Shapes combine by np.minimum (union) and np.maximum (intersection; of phi and -psi:
+        phi with psi cut out)."""
+        x, y = self.coords()
+        X, Y = np.meshgrid(x, y, indexing="ij")
+        if self.is_reference_ellipse():
+            return X * X + 4.0 * Y * Y - 1.0
+        return (X / self.ax) ** 2 + (Y / self.by) ** 2 - 1.0
+
     def _host_array(self, a, name: str, writable: bool = False, apply_hint: bool = True) -> np.ndarray:
         """field()'s type, dtype and shape rules without its finiteness scan (apply's arguments, whose refusal of
         a device tensor points to Session.apply)."""
@@ -195,7 +217,7 @@ class PoissonEllipse:
         return a
 
     def apply(self, x, out=None, *, alpha: float = 1.0, beta: float = 0.0, y=None, gamma: float = 1.0,
-              const: float = 0.0, reaction=None, diffusion=None) -> np.ndarray:
+              const: float = 0.0, reaction=None, diffusion=None, domain=None) -> np.ndarray:
         """alpha L x + beta x + gamma y + const on the interior nodes and 0 on the box boundary, on the host
         (the CPU oracle's stencil); L = A + sigma I with this problem's sigma, the plain matrix on the whole
         box -- fictitious region included, no ellipse mask.  The host twin of Session.apply: NumPy arrays
@@ -207,10 +229,14 @@ class PoissonEllipse:
         a session built with that field.
 
         diffusion: optional nodal field k(x, y) > 0 (diffusion_field()'s rules): A becomes -div(k grad .) with
-        the face coefficients (0.5 (k + k')) a, (0.5 (k + k')) b of the two nodes of a face."""
+        the face coefficients (0.5 (k + k')) a, (0.5 (k + k')) b of the two nodes of a face.
+
+        domain: optional level-set field phi (domain_field()'s rules): a, b are the faces of D = {phi < 0} instead
+        of the ellipse's (see solve()); still the matrix on the whole box, no mask."""
         xa = self._host_array(x, "x")
         ca = self.reaction_field(reaction)
         ka = self.diffusion_field(diffusion)
+        pa = self.domain_field(domain)
         ya = None if y is None else self._host_array(y, "y")
         oa = None if out is None else self._host_array(out, "out", writable=True)
         for name, v in (("alpha", alpha), ("beta", beta), ("gamma", gamma), ("const", const)):
@@ -220,19 +246,22 @@ class PoissonEllipse:
             raise ValueError("out overlaps x")
         r = _native().cpu_apply(self.to_native(), np.ascontiguousarray(xa),
                                 None if ya is None else np.ascontiguousarray(ya), float(alpha), float(beta),
-                                float(gamma), float(const), reaction=ca, diffusion=ka)
+                                float(gamma), float(const), reaction=ca, diffusion=ka, domain=pa)
         if oa is None:
             return r
         oa[...] = r
         return oa
 
-    def error_norms(self, w: np.ndarray, exact: Optional[np.ndarray] = None) -> dict:
+    def error_norms(self, w: np.ndarray, exact: Optional[np.ndarray] = None, domain=None) -> dict:
         """L2 (h-weighted) and max error of a (M+1)x(N+1) solution in D, vs the analytic solution of the
-        constant-F problem or, for another right-hand side, vs `exact` ((M+1)x(N+1) values of its solution)."""
+        constant-F problem or, for another right-hand side, vs `exact` ((M+1)x(N+1) values of its solution).
+        domain: the level-set field of the solve: D is its mask, and `exact` is required (ValueError without)."""
         x, y = self.coords()
         X, Y = np.meshgrid(x, y, indexing="ij")
+        if exact is None:
+            self.require_closed_form("error_norms", domain)
         u = self.exact_solution(X, Y) if exact is None else self.field(exact, "exact")
-        m = self.inside_mask()
+        m = self.inside_mask(domain)
         e = np.where(m, w - u, 0.0)
         return {
             "l2_error": float(math.sqrt(float((e * e).sum()) * self.h1 * self.h2)),

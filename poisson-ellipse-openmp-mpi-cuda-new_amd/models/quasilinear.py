@@ -30,7 +30,10 @@ class QuasilinearPicard:
     breakdown_tol=0 with tight tolerances), or the Picard residual stalls at the accuracy of the inner solve.
 
     After solve(): `history` (residuals, one per step taken plus the final one), `steps` (linear solves),
-    `converged`, `last` (statistics of the last linear solve)."""
+    `converged`, `last` (statistics of the last linear solve).
+
+    domain=phi in session_kw (solve()'s level-set field) poses the problem on D = {phi < 0}: every step calls
+    Session.set_domain(phi, diffusion=κ(u_k)) on hip, and the residual's mask is that of phi."""
 
     def __init__(self, problem: PoissonEllipse, kappa, backend: str = "hip", picard_rtol: float = 1e-8,
                  max_picard: int = 50, **session_kw):
@@ -52,7 +55,8 @@ class QuasilinearPicard:
 
     def _residual_host(self, u, f, k) -> float:
         p = self.problem
-        e = np.where(p.inside_mask(), f, 0.0) - p.apply(u, reaction=self.kw.get("reaction"), diffusion=k)
+        phi = self.kw.get("domain")
+        e = np.where(p.inside_mask(phi), f, 0.0) - p.apply(u, reaction=self.kw.get("reaction"), diffusion=k, domain=phi)
         e[0, :] = e[-1, :] = 0.0
         e[:, 0] = e[:, -1] = 0.0
         return math.sqrt(float((e * e).sum()) * p.h1 * p.h2)
@@ -70,6 +74,8 @@ class QuasilinearPicard:
             if hip:
                 if self.session is None:
                     self.session = make_session(self.problem, diffusion=k, **self.kw)
+                elif self.session.has_domain:  # the faces are refolded from phi and k together
+                    self.session.set_domain(self.kw["domain"], diffusion=k)
                 else:
                     self.session.set_diffusion(k)
                 if self.steps == 0:

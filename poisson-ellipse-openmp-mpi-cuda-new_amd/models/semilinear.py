@@ -29,7 +29,10 @@ class SemilinearNewton:
     breakdown_tol=0 with tight tolerances), or the Newton residual stalls at the accuracy of the inner solve.
 
     After solve(): `history` (residuals, one per step taken plus the final one), `steps` (linear solves),
-    `converged`, `last` (statistics of the last linear solve)."""
+    `converged`, `last` (statistics of the last linear solve).
+
+    domain=phi in session_kw (solve()'s level-set field) poses the problem on D = {phi < 0}: the solves and the
+    residual's mask take it."""
 
     def __init__(self, problem: PoissonEllipse, g, dg, backend: str = "hip", newton_rtol: float = 1e-8,
                  max_newton: int = 20, **session_kw):
@@ -50,7 +53,8 @@ class SemilinearNewton:
 
     def _residual_host(self, u, rhs, c) -> float:
         p = self.problem
-        e = np.where(p.inside_mask(), rhs, 0.0) - p.apply(u, reaction=c)
+        phi = self.kw.get("domain")
+        e = np.where(p.inside_mask(phi), rhs, 0.0) - p.apply(u, reaction=c, domain=phi)
         e[0, :] = e[-1, :] = 0.0
         e[:, 0] = e[:, -1] = 0.0
         return math.sqrt(float((e * e).sum()) * p.h1 * p.h2)

@@ -71,7 +71,18 @@ def solve(problem: PoissonEllipse, backend: str = "hip", **kw) -> Result:
     (the faces next to the box boundary read its boundary values): the solve is (-∇·k∇ + σ + c) u = f.  The face
     coefficients become (0.5 (k[i-1,j] + k[i,j])) a[i,j] and (0.5 (k[i,j-1] + k[i,j])) b[i,j] -- the fictitious
     1/ε included, so the medium outside D is k/ε -- and D, A x and the stop rules are the same algebra on them.
-    k = 1 is the solve without the argument, bitwise on the CPU backends.  hip: under reaction's rules."""
+    k = 1 is the solve without the argument, bitwise on the CPU backends.  hip: under reaction's rules.
+
+    domain (every backend): an (M+1)x(N+1) float64 field phi(x, y) of nodal level-set values, finite on every node:
+    D = {phi < 0} replaces the ellipse.  In fp64, in this order: phi_c[i,j] = 0.25 ((phi[i-1,j-1] + phi[i-1,j]) +
+    (phi[i,j-1] + phi[i,j])) at the cell centres; the inside fraction of a face with end values p, q is 1 if both
+    are < 0, 0 if neither is, else n / (n - m) with n the negative one -- ONE linear crossing per face, so features
+    thinner than a cell are not resolved; the coefficient is theta + (1 - theta) / eps, without the ellipse's 1e-9
+    snapping; a[i,j] takes phi_c[i,j], phi_c[i,j+1] and b[i,j] takes phi_c[i,j], phi_c[i+1,j].  The right-hand side
+    is masked by phi[i,j] < 0.  diffusion scales these faces as it scales the ellipse's, and without it the solve is
+    that of k = 1, bitwise.  A component of the complement of D that does not touch the box boundary is no Dirichlet
+    hole: nothing anchors u there and it floats to a constant; pin it with reaction=np.where(hole, 1e8, 0).
+    PoissonEllipse.ellipse_levelset() is the ellipse as such a field.  hip: under diffusion's rules."""
     if backend in ("cpu", "serial"):
         return solve_cpu(problem, threads=1, **kw)
     if backend in ("omp", "openmp"):
@@ -94,19 +105,20 @@ def _residual_extra(r) -> dict:
 
 
 def solve_cpu(problem: PoissonEllipse, threads: int = 1, keep_solution: bool = True, rhs=None, w0=None,
-              reaction=None, diffusion=None) -> Result:
+              reaction=None, diffusion=None, domain=None) -> Result:
     r = _native().cpu_solve(problem.to_native(), int(threads), bool(keep_solution), rhs=rhs, w0=w0,
-                            reaction=reaction, diffusion=diffusion)
+                            reaction=reaction, diffusion=diffusion, domain=domain)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
                   backend="cpu" if threads <= 1 else f"omp{threads}", extra=_residual_extra(r))
 
 
 def solve_cpu_decomposed(problem: PoissonEllipse, ranks: int = 4, split: str = "reference",
                          threads: int = 1, keep_solution: bool = True, rhs=None, w0=None,
-                         reaction=None, diffusion=None) -> Result:
+                         reaction=None, diffusion=None, domain=None) -> Result:
     n = _native()
     r = n.cpu_solve_decomposed(problem.to_native(), int(ranks), getattr(n.Split, split), int(threads),
-                               bool(keep_solution), rhs=rhs, w0=w0, reaction=reaction, diffusion=diffusion)
+                               bool(keep_solution), rhs=rhs, w0=w0, reaction=reaction, diffusion=diffusion,
+                               domain=domain)
     return Result(r["iters"], r["status"], r["diff"], r["seconds"], r.get("w"),
                   backend="cpu-decomposed", ranks=ranks, extra=_residual_extra(r))
 
@@ -117,7 +129,7 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
                  overlap: bool = True, vec_b: int = 0, waves_b: int = 0, tile_rows_b: int = -1,
                  poison_halos: bool = False, b_ring: bool = False, placement: int = 0,
                  placement_budget_s: float = 0.5, placement_keep_free: float = 0.5, block_tiles: int = -1,
-                 algo: str | int = -1, ca_s: int = 3, reaction=None, diffusion=None):
+                 algo: str | int = -1, ca_s: int = 3, reaction=None, diffusion=None, domain=None):
     """Native GPU session with `ranks` subdomains on one device (LocalComm when ranks > 1).
 
     overlap: ghost exchange on a second stream concurrent with pcg_b (only matters for ranks > 1).
@@ -156,7 +168,15 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
     (which a diffusion session always holds: T(σ + c), c = 0 without reaction); its sweeps read them in place of
     the 1-D tables.  dtype "fp32" runs the mixed arithmetic (fp32 fields, fp64 registers) on such a session.
     Session.set_diffusion(k) replaces the fields in place, as set_reaction does; the refusals of reaction
-    apply."""
+    apply.
+
+    domain: an (M+1)x(N+1) float64 level-set field phi, finite on every node (the same kinds of objects): D =
+    {phi < 0} replaces the ellipse, see solve().  A domain session is a diffusion session -- k = 1 without
+    diffusion, bitwise the session with diffusion=ones -- whose face-coefficient fields hold the faces of D (one
+    setup kernel reads phi, on the device, across subdomain borders), plus one mask byte per owned node for the
+    right-hand side; phi is not retained.  Session.set_domain(phi, diffusion=None) replaces faces and mask in place
+    (a moving domain on captured graphs); set_diffusion raises on such a session, since the faces cannot be
+    refolded without phi.  The refusals of diffusion apply."""
     n = _native()
     algo = {"auto": -1, "pcg1": 1, "pcg2": 2, "ca": 3}.get(algo, algo) if isinstance(algo, str) else algo
     return n.Session(problem.to_native(), world=int(ranks), comm="self" if ranks == 1 else "local",
@@ -166,7 +186,7 @@ def make_session(problem: PoissonEllipse, ranks: int = 1, split: str = "referenc
                      poison_halos=poison_halos, b_ring=b_ring, placement=placement,
                      placement_budget_s=placement_budget_s, placement_keep_free=placement_keep_free,
                      block_tiles=block_tiles, algo=int(algo), ca_s=int(ca_s), reaction=reaction,
-                     diffusion=diffusion)
+                     diffusion=diffusion, domain=domain)
 
 
 def solve_hip(problem: PoissonEllipse, ranks: int = 1, keep_solution: bool = True, poll_batches: int = 1,

@@ -80,10 +80,13 @@ def moment_gram(Y: list, D: torch.Tensor, s: int, h: float) -> torch.Tensor:
 
 
 class TorchSStepPCG:
-    def __init__(self, problem, s: int = 3, device="cpu", gram: str = "moments", reaction=None, diffusion=None):
+    def __init__(self, problem, s: int = 3, device="cpu", gram: str = "moments", reaction=None, diffusion=None,
+                 domain=None):
         self.gram = gram
         if s < 1:
             raise ValueError("s must be >= 1")
+        if domain is not None:
+            raise ValueError("the s-step PCG is not built for a level-set domain")
         if reaction is not None:
             raise ValueError("the s-step PCG is not built for a reaction field")
         if diffusion is not None:

@@ -17,7 +17,8 @@ class BackwardEuler:
     (M+1) x (N+1) float64; g may be a scalar.  The problem's stop rule carries over: with stop="residual"
     every step solves to rtol relative to its own right-hand side u/dt + g, not to the already small
     residual of its start w0 = u.  reaction=c in session_kw (make_session's / solve()'s field, every backend)
-    steps u_t = Δu - c u + g; diffusion=k likewise steps u_t = ∇·(k∇u) + g (variable conductivity)."""
+    steps u_t = Δu - c u + g; diffusion=k likewise steps u_t = ∇·(k∇u) + g (variable conductivity); domain=phi
+    poses either on D = {phi < 0} instead of the ellipse."""
 
     def __init__(self, problem: PoissonEllipse, dt: float, backend: str = "hip", **session_kw):
         if not (isinstance(dt, (int, float)) and math.isfinite(dt) and dt > 0):
@@ -57,7 +58,8 @@ class ThetaScheme:
     a NumPy array out.  Every other backend of solve() takes and returns NumPy arrays.  All fields are
     (M+1) x (N+1) float64.  `last` holds the statistics of the last step's solve, and the problem's stop rule
     carries over as in BackwardEuler.  reaction=c in session_kw adds the field to L, on both sides of the step:
-    the solve and the apply of the right-hand side; diffusion=k likewise makes A the k operator on both sides."""
+    the solve and the apply of the right-hand side; diffusion=k likewise makes A the k operator on both sides, and
+    domain=phi the operator (and the mask) of D = {phi < 0}."""
 
     def __init__(self, problem: PoissonEllipse, dt: float, theta: float = 0.5, backend: str = "hip", **session_kw):
         if not (isinstance(dt, (int, float)) and math.isfinite(dt) and dt > 0):
@@ -86,7 +88,8 @@ class ThetaScheme:
         on_device = hasattr(u, "__cuda_array_interface__")
         if on_device and self.session is not None:
             return self.session.apply(u, **kw)  # the session's operator: its reaction field included
-        return self.problem.apply(u, reaction=self.kw.get("reaction"), diffusion=self.kw.get("diffusion"), **kw)
+        return self.problem.apply(u, reaction=self.kw.get("reaction"), diffusion=self.kw.get("diffusion"),
+                                  domain=self.kw.get("domain"), **kw)
 
     def step(self, u, g=None):
         rhs = self.rhs(u, g)

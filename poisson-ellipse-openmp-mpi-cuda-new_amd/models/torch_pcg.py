@@ -20,11 +20,13 @@ from .solvers import Result
 
 class TorchPCG:
     def __init__(self, problem, device="cpu", dtype=torch.float64, comm=None, split="reference", reaction=None,
-                 diffusion=None):
+                 diffusion=None, domain=None):
         """reaction: optional global (M+1)x(N+1) float64 field c >= 0 (NumPy or a CPU tensor; boundary values
         ignored): the operator is A + (sigma + c) I, the diagonal D + sigma + c.
         diffusion: optional global (M+1)x(N+1) float64 field k > 0 on every node: the face coefficients are
-        multiplied by the mean of k over the two nodes of the face (ops.reference.assemble)."""
+        multiplied by the mean of k over the two nodes of the face (ops.reference.assemble).
+        domain: optional global (M+1)x(N+1) float64 level-set field phi: D = {phi < 0} replaces the ellipse in the
+        faces and in the right-hand-side mask (ops.reference.assemble)."""
         self.p = problem
         self.comm = comm or SingleComm()
         self.device = torch.device(device)
@@ -32,7 +34,9 @@ class TorchPCG:
         Px, Py = process_grid(self.comm.world, problem.M, problem.N, split)
         self.sd = subdomain(problem.M, problem.N, Px, Py, self.comm.rank)
         self.a, self.b, self.B = R.assemble(problem, self.sd, self.device, dtype,
-                                            diffusion=problem.diffusion_field(diffusion))
+                                            diffusion=problem.diffusion_field(diffusion),
+                                            domain=problem.domain_field(domain))
+        self.domain = problem.domain_field(domain)
         self.nbs = neighbours(self.sd)
         self.shift = problem.sigma  # a number, or with a reaction field the (nx, ny) tensor sigma + c
         c = problem.reaction_field(reaction)
@@ -75,7 +79,8 @@ class TorchPCG:
         self.w = torch.zeros(self.B.shape, dtype=self.dtype, device=self.device)
         self.r = self.B.clone()
         if rhs is not None:
-            inside = R.inside(P, self.sd, self.device)
+            inside = R.inside(P, self.sd, self.device) if self.domain is None else \
+                R.inside_domain(P, self.sd, self.domain, self.device)
             self.r = torch.where(inside, self._local(rhs), torch.zeros_like(self.B))
             for edge in (self.r[0, :], self.r[-1, :], self.r[:, 0], self.r[:, -1]):
                 edge.zero_()

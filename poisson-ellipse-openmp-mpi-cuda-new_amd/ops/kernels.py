@@ -12,7 +12,12 @@ from ..utils.native import load as _native
 
 
 class DeviceOps:
-    def __init__(self, problem, Px: int = 1, Py: int = 1, rank: int = 0, device: int = 0, reaction=None, diffusion=None):
+    def __init__(self, problem, Px: int = 1, Py: int = 1, rank: int = 0, device: int = 0, reaction=None, diffusion=None,
+                 domain=None):
+        if domain is not None:
+            raise ValueError("DeviceOps forms its faces from the ellipse's tables: not built for a level-set domain "
+                             "(use a native session: solve(problem, 'hip', domain=phi) / make_session(problem, "
+                             "domain=phi))")
         if diffusion is not None:
             raise ValueError("DeviceOps evaluates -div(grad u) with k = 1 alone: not built for a diffusion field (use a "
                              "native session: solve(problem, 'hip', diffusion=k) / make_session(problem, diffusion=k))")

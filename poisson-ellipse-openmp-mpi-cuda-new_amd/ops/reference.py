@@ -58,24 +58,39 @@ def inside(problem, sd, device="cpu"):
     return (x / problem.ax) ** 2 + (y / problem.by) ** 2 < 1.0
 
 
-def assemble(problem, sd, device="cpu", dtype=torch.float64, diffusion=None):
+def inside_domain(problem, sd, domain, device="cpu"):
+    """inside() for a level-set field: phi < 0 over the local array incl. ghosts (ghosts beyond the box: False)."""
+    gi, gj = local_index(sd)
+    ok = ((gi >= 0) & (gi <= problem.M))[:, None] & ((gj >= 0) & (gj <= problem.N))[None, :]
+    phi = torch.as_tensor(domain, dtype=torch.float64)[gi.clamp(0, problem.M)][:, gj.clamp(0, problem.N)]
+    return ((phi < 0) & ok).to(device)
+
+
+def assemble(problem, sd, device="cpu", dtype=torch.float64, diffusion=None, domain=None):
     """a, b over the local array incl. ghosts, B (RHS) on the interior.  Shapes (nx+2, ny+2).
     diffusion: optional global (M+1)x(N+1) float64 field k > 0 of nodal values: a[i,j] <- (0.5 (k[i-1,j] +
     k[i,j])) a[i,j], b[i,j] <- (0.5 (k[i,j-1] + k[i,j])) b[i,j] in fp64, on the faces between two nodes of the
-    box."""
-    T = face_tables(problem, device)
+    box.
+    domain: optional global (M+1)x(N+1) float64 level-set field phi: a, b are the faces of D = {phi < 0} (the
+    native cpu_assemble's, geometry.hpp's ls_coef_a / ls_coef_b) and B is masked by phi < 0."""
     gi, gj = local_index(sd)
     gi, gj = gi.to(device), gj.to(device)
-    ylo, yhi, rv = T["ylo"][gj][None, :], T["yhi"][gj][None, :], T["rv"][gi][:, None]
-    xlo, xhi, rh = T["xlo"][gi][:, None], T["xhi"][gi][:, None], T["rh"][gj][None, :]
-    a = _face_coef(_clip_len(ylo, yhi, rv), problem.h2, problem.eps)
-    b = _face_coef(_clip_len(xlo, xhi, rh), problem.h1, problem.eps)
+    if domain is not None:
+        ga, gb, _ = _native().cpu_assemble(problem.to_native(), domain=domain)  # (M+2) x (N+2), global index
+        a = torch.as_tensor(ga, dtype=torch.float64).to(device)[gi][:, gj]
+        b = torch.as_tensor(gb, dtype=torch.float64).to(device)[gi][:, gj]
+    else:
+        T = face_tables(problem, device)
+        ylo, yhi, rv = T["ylo"][gj][None, :], T["yhi"][gj][None, :], T["rv"][gi][:, None]
+        xlo, xhi, rh = T["xlo"][gi][:, None], T["xhi"][gi][:, None], T["rh"][gj][None, :]
+        a = _face_coef(_clip_len(ylo, yhi, rv), problem.h2, problem.eps)
+        b = _face_coef(_clip_len(xlo, xhi, rh), problem.h1, problem.eps)
     if diffusion is not None:
         k = torch.as_tensor(diffusion, dtype=torch.float64).to(device)
         kc = k[gi][:, gj]
         a = torch.where((gi >= 1)[:, None], (0.5 * (k[(gi - 1).clamp(min=0)][:, gj] + kc)) * a, a)
         b = torch.where((gj >= 1)[None, :], (0.5 * (k[gi][:, (gj - 1).clamp(min=0)] + kc)) * b, b)
-    mask = inside(problem, sd, device)
+    mask = inside(problem, sd, device) if domain is None else inside_domain(problem, sd, domain, device)
     B = torch.where(mask, torch.full_like(a, problem.F), torch.zeros_like(a))
     B[0, :] = 0
     B[-1, :] = 0

@@ -98,7 +98,8 @@ class DistGpuPCG:
                  overlap: bool = True, vec_b: int = 0, waves_b: int = 0, tile_rows_b: int = -1,
                  b_ring: bool = False, algo: int = -1, init_timeout: float = 90.0, device: int | None = None,
                  placement: int = 0, placement_budget_s: float = 0.5, placement_keep_free: float = 0.5,
-                 phase=None, ca_s: int = 3, split_sweep: int = -1, reaction=None, diffusion=None):
+                 phase=None, ca_s: int = 3, split_sweep: int = -1, reaction=None, diffusion=None,
+                 domain=None):
         """placement: candidate field blocks of the placement probe (0 = off; forced off when ranks share
         a device).  phase(name, seconds): progress-watchdog hook (bench.py's Watch.phase); called with
         "comm-init" before the blocking communicator initialisation, whose own watchdog is
@@ -106,6 +107,11 @@ class DistGpuPCG:
         the compute stream in a fixed order.  algo: -1 = auto (the library's choose_algo: the s-step
         PCG on big fp64 row strips where its fields fit), 1 / 2 / 3; ca_s: the s-step block size;
         split_sweep: pcg1's split sweep (-1 = the transport's default, 0 off, 1 on)."""
+        if domain is not None:
+            raise ValueError("DistGpuPCG is not built for a level-set domain: neither the Python-orchestrated path "
+                             "(comm='torch') nor the multi-process transports hold face-coefficient fields or a "
+                             "mask; use a session that owns every subdomain (make_session(problem, ranks=..., "
+                             "domain=phi))")
         if diffusion is not None:
             raise ValueError("DistGpuPCG is not built for a diffusion field: neither the Python-orchestrated path "
                              "(comm='torch') nor the multi-process transports hold face-coefficient fields; use a "
